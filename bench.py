@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: decoded terrain megapixels / second at fixed steps (BASELINE.json), terrain-diffusion-30m base model.
 
-    python bench.py --gpus N --steps K --warmup W [--workload grid8|grid32|tiles|cascade] [--dtype bf16|fp32]
+    python bench.py --gpus N --steps K --warmup W [--workload grid8|grid32|tiles|cascade] [--dtype bf16|fp32] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input, inputs resident in HBM:
   grid8  (default at N=1, BASELINE configs[2]): an 8x8 grid of overlapping 64x64-latent windows (stride 32) on a 288x288 latent
@@ -10,11 +10,19 @@ A "step" is one pass of the hot path over one batch of synthetic input, inputs r
          ranks as a 2-D block mesh with the point-to-point seam exchange of window outputs over RCCL (terrain_diffusion_amd/parallel.py);
          total work is fixed -> "scaling": "strong".  The line carries the seam bytes and the exchange time.
   tiles  (BASELINE configs[1] batched): 64 INDEPENDENT single-tile jobs per step (no overlap): 16.78 decoded MP; N>1: every rank its own
-         batch (weak).  The literal configs[1] number (ONE tile, latency-bound) is reported on every N=1 line as "latency_single_tile_ms".
+         batch (weak).  The literal configs[1] number (ONE tile, latency-bound) is reported on every N=1 --full line as "latency_single_tile_ms".
   cascade (BASELINE configs[4] shapes on one GPU): coarse -> 2-phase latent -> decoder through the lazy InfiniteTensor graph with a capped
          tile cache; see run_cascade().
 With --gpus N > 1 and no WORLD_SIZE in the environment bench.py launches its own N ranks (torch.distributed.run, 127.0.0.1).
 Weights are synthetic (portable-RNG seeded, out_gain=1, emb_gain=0.5): there is no network for checkpoints.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (value, ms_per_step and the end-to-end roofline figure derived from them).
+--full adds the legs that take runs of their own: the per-kernel profile step and the kernel-level roofline, the single-tile latency leg, the
+grid32 strong-scaling anchor and the CPU baseline (cascade: the batch sweep and the per-stage kernel profile of one request); --no-kernel-profile,
+--no-latency and --no-cpu-baseline drop single legs of a --full run.
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32): the blended canvas (grid8, grid32), the
+(n, 5, 64, 64) tiles (tiles), the elevation and climate of the last request (cascade); with N > 1 every rank writes <name>_rank<r>.npy.  Inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -34,6 +42,7 @@ PEAK_BF16_TFLOPS = 2500.0            # MI355X dense bf16 MFMA (MI355X_MICROARCH.
 PEAK_F32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
 PROFILE_JSON = os.path.join(ROOT, "profiles", "r06_hbm_traffic_and_mfma_util.json")   # stamped with the library build id it was collected with
+DUMP_BUDGET_BYTES = 60 * 2 ** 20     # --dump-outputs: array bytes in all (over all ranks), under 64 MB with the .npy headers
 
 # terrain-diffusion-30m base model (configs/diffusion_base/30m/diffusion_192-3.cfg:54-68)
 BASE_CONFIG = dict(image_size=512, in_channels=5, out_channels=5, model_channels=192, model_channel_mults=[1, 2, 3, 4], layers_per_block=3,
@@ -56,7 +65,35 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-tile latency leg (keeps rocprofv3 counter passes to the batched steps only)")
+    ap.add_argument("--full", action="store_true", help="also run the extra legs: kernel profile + kernel-level roofline, single-tile latency, strong-scaling "
+                                                        "anchor, CPU baseline (cascade: batch sweep, per-stage kernel profile); off = only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32, under 64 MB in all)")
     return ap.parse_args()
+
+
+def dump_outputs(dirpath, arrays, rank=0, world=1):
+    """--dump-outputs: every array as dirpath/<name>.npy in float32 (float64 stays float64), <name>_rank<r> when N > 1.  Past the byte budget
+    (DUMP_BUDGET_BYTES shared by the ranks) an array is replaced by a fixed, seeded sample of its flattened elements (same indices on every run of
+    the same shape), so that the files stay comparable between builds."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // world
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        if isinstance(t, torch.Tensor):
+            t = t.detach()
+            a = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        else:
+            a = np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > left:
+            k = max(0, left // a.itemsize)
+            idx = np.sort(np.random.default_rng(0x5EED).integers(0, a.size, size=k))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(dirpath, (f"{name}_rank{rank}" if world > 1 else name) + ".npy"), a)
 
 
 def self_launch(args):
@@ -130,8 +167,9 @@ def main():
     nt = len(_tile_starts(H, 64, 32))
     cond = synthetic_cond_grid(nt, nt, device=dev)
     kw = dict(cond_means=torch.zeros(7), cond_stds=torch.ones(7), noise_level=torch.tensor(0.0), histogram_raw=torch.zeros(1, 5), steps=E, tile_size=64)
+    # per-tile conditioning of the tiles workload (and of the single-tile / anchor legs of --full)
     cond58 = torch.cat([_process_cond_img(synthetic_cond_grid(1, 1, seed=0xC0DE + j, device=dev), torch.zeros(1, 5), torch.zeros(7), torch.ones(7), 0.0)
-                        for j in range(max(1, args.tiles_per_step))])
+                        for j in range(max(1, args.tiles_per_step))]) if (workload == "tiles" or args.full) else None
     seam = {}
     strong = workload == "grid32"
     if strong and "batch_invariant=" not in args.engine_opts:
@@ -180,6 +218,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert bool(torch.isfinite(out).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tiles" if workload == "tiles" else "canvas": out}, rank, world)
     ms_per_step = dt / args.steps * 1e3
     weak_factor = 1 if (strong or world == 1) else world   # grid8 / tiles at N>1: every rank its own canvas / batch
     value = weak_factor * args.steps * mp_per_step / dt
@@ -212,7 +252,7 @@ def main():
         e2e_tflops = flop_per_step / (ms_per_step * 1e-3) / 1e12
         roof = {"bound": "mfma", "kernel": "td::conv_glds_kernel", "peak": peak, "unit": "TFLOP/s", "traffic": None,
                 "end_to_end_achieved": round(e2e_tflops, 2), "end_to_end_frac": round(e2e_tflops / peak, 4)}
-        if not args.no_kernel_profile and world == 1:
+        if args.full and not args.no_kernel_profile and world == 1:
             # kernel level: HIP events on the engine's own stream around every conv launch (eager mode, no graph), one extra step
             # (one lane, whatever the timed region used: every kernel at the FULL batch, one after the other -- what `rocprofv3 --kernel-trace` of
             # `bench.py --engine-opts dual_stream=0` sees; two lanes are accounted for below)
@@ -293,7 +333,7 @@ def main():
         else:
             roof.update({"achieved": roof["end_to_end_achieved"], "frac": roof["end_to_end_frac"]})
         result["roofline"] = roof
-        if world == 1 and not args.no_latency:
+        if args.full and world == 1 and not args.no_latency:
             # BASELINE configs[1] as written: ONE tile through the same path (batch 1: weight-streaming / launch-latency bound, not MFMA bound)
             one_step(20_000, 1, "tiles"); sync()
             l0 = time.perf_counter()
@@ -310,7 +350,7 @@ def main():
                                               "note": f"algorithmic bytes = {E} forwards x {WEIGHT_BYTES_BF16} B of bf16 weights (activations of one tile are negligible); "
                                                       "measured HBM bytes per forward: profiles/r06_batch1_hbm_traffic.json"}
 
-        if world == 1 and not args.no_latency and workload == "grid8" and args.dtype == "bf16":
+        if args.full and world == 1 and not args.no_latency and workload == "grid8" and args.dtype == "bf16":
             # N = 1 point of the STRONG-scaling workload the driver runs at N > 1 (grid32, BASELINE configs[3]): one full step, timed live in this
             # run with the same engine options the sharded run uses, so that the 1 -> N curve has a same-run, same-node anchor
             from terrain_diffusion_amd.parallel import sample_base_diffusion_sharded
@@ -334,7 +374,7 @@ def main():
             finally:
                 pass
 
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # CPU baseline = the oracle (CPU restatement pinned to the reference) on this host's cores, bounded sample
             # (the only place bench.py touches oracle/: the checker is what is timed here, never the product path)
             from oracle import tiling

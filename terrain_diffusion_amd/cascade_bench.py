@@ -80,6 +80,10 @@ def run_cascade(args, eng, dev, rank, world):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert out is None or bool(torch.isfinite(out["elev"]).all())
+    if getattr(args, "dump_outputs", None) and out is not None:
+        from bench import dump_outputs
+        dump_outputs(args.dump_outputs, {"elev": out["elev"], "climate": out["climate"]}, rank, world)
+    full = bool(getattr(args, "full", False))
     per_rank = [split.get("requests_this_rank", 0)]
     if world > 1:   # the request split of the replica mode, rank by rank (make the N > 1 cascade line say who served what)
         pr = torch.zeros(world, dtype=torch.int64, device=dev); pr[rank] = per_rank[0]
@@ -88,7 +92,7 @@ def run_cascade(args, eng, dev, rank, world):
     # the regime between the two legs the driver line reports (batch 1 and batch 64): the base U-Net's forward at the batch sizes the latent stage
     # actually runs (latents_batch_size 1 ... 64), wall time per forward of eager launches on the engine stream
     sweep = {}
-    if rank == 0:
+    if full and rank == 0:
         base = models[1]
         for nb in (1, 8, 32):
             x = td.standard_normal(7, (nb, 5, 64, 64), device=dev, as_torch=True); c = td.standard_normal(8, (nb, 58), device=dev, as_torch=True); tt_ = torch.full((nb,), 1.1)
@@ -101,14 +105,16 @@ def run_cascade(args, eng, dev, rank, world):
             sweep[str(nb)] = {"ms_per_forward": round(ms_f, 3), "tflops": round(nb * 193.654 / ms_f, 1)}
     mp = R * R / 1e6
     value = args.steps * mp / dt
-    # per-stage kernel time: one profiled (eager) request of fresh terrain
-    eng.set_option("profile", 1)
-    eng.profile_read(reset=True)
-    world_p.get(7_000_000, 7_000_000, 7_000_000 + Q, 7_000_000 + Q)
-    sync()
-    ops = eng.profile_ops()
-    conv_ms, conv_n, other_ms, other_n = eng.profile_read(reset=True)
-    eng.set_option("profile", 0)
+    # per-stage kernel time (--full): one profiled (eager) request of fresh terrain
+    ops, conv_ms, other_ms = [], 0.0, 0.0
+    if full:
+        eng.set_option("profile", 1)
+        eng.profile_read(reset=True)
+        world_p.get(7_000_000, 7_000_000, 7_000_000 + Q, 7_000_000 + Q)
+        sync()
+        ops = eng.profile_ops()
+        conv_ms, conv_n, other_ms, other_n = eng.profile_read(reset=True)
+        eng.set_option("profile", 0)
     import re
     by_level, mb_level = {}, {}
     for label, ms, n in ops:
@@ -132,11 +138,14 @@ def run_cascade(args, eng, dev, rank, world):
                    "cache_evictions_per_step": round((world_p.tile_store.evictions - ev0) / args.steps, 1),
                    "requests_per_step": split.get("requests_per_step"), "requests_per_rank": per_rank,
                    "engine_calls": "enqueue-only on one stream shared with torch (Engine.on_stream)" if enqueue_only else "synchronous (complete on return)"},
-        "batch_sweep": {"what": "base U-Net forward (193.654 GFLOP per tile) at the latent stage's batch sizes, eager launches, wall ms per forward; "
-                                "the full 1 ... 64 sweep with HBM bytes is profiles/r05_batch_sweep.txt", "by_batch": sweep},
         "roofline": {"bound": "mfma", "kernel": "td::conv_glds_kernel (all stages)", "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "achieved": round(tflops, 2),
                      "frac": round(tflops / PEAK_BF16_TFLOPS, 4), "traffic": None,
-                     "note": "end to end over the algorithmic 15.24 TFLOP per decoded MP (recomputed evicted windows are NOT counted as useful work)",
+                     "note": "end to end over the algorithmic 15.24 TFLOP per decoded MP (recomputed evicted windows are NOT counted as useful work)"},
+    }
+    if full:
+        result["batch_sweep"] = {"what": "base U-Net forward (193.654 GFLOP per tile) at the latent stage's batch sizes, eager launches, wall ms per forward; "
+                                         "the full 1 ... 64 sweep with HBM bytes is profiles/r05_batch_sweep.txt", "by_batch": sweep}
+        result["roofline"].update({
                      "one_request_conv_kernel_ms": round(conv_ms, 2), "one_request_other_kernel_ms": round(other_ms, 2),
                      "one_request_kernel_ms_by_resolution": {k: round(v, 2) for k, v in sorted(by_level.items())},
                      # achieved HBM GB/s of the conv path by resolution level: algorithmic megabytes of the level's launches (sources, residual, outputs and
@@ -144,7 +153,6 @@ def run_cascade(args, eng, dev, rank, world):
                      # activation-bound one (~288 FLOP/B, below the 312 FLOP/B ridge of 2.5 PF over 8 TB/s)
                      "hbm_gbps_by_resolution": {k: round(v[0] / v[1], 1) for k, v in sorted(mb_level.items()) if v[1] > 0},
                      "hbm_gbps_decoder_512x512": round(mb_level["512x512"][0] / mb_level["512x512"][1], 1) if mb_level.get("512x512", [0, 0])[1] > 0 else None,
-                     "hbm_peak_gbps": 8000.0},
-    }
+                     "hbm_peak_gbps": 8000.0})
     if rank == 0:
         print(json.dumps(result), flush=True)

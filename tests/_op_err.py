@@ -1,5 +1,5 @@
 import sys, numpy as np, torch, torch.nn.functional as F
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os; _T = os.path.dirname(os.path.abspath(__file__)); sys.path.insert(0, os.path.dirname(_T)); sys.path.insert(0, _T)
 import terrain_diffusion_amd as td
 from conftest import rel_rms
 from oracle import rng

@@ -190,3 +190,22 @@ def test_unsupported_constructor_arguments_are_refused_before_the_engine_starts(
     for bad in (dict(noise_emb_dims=0), dict(fourier_scale=1), dict(encode_only=True), dict(conditional_inputs=[["embedding", 10, 1.0]])):
         with pytest.raises(NotImplementedError):
             td.EDMUnet2D(**{**base, **bad})
+
+
+def test_bench_dump_outputs_writes_float32_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: float32 (float64 kept) .npy files named after the outputs; past the byte budget an output is replaced by a fixed,
+    seeded sample of its elements, the same on every call, and the files stay under 64 MB in all."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_BUDGET_BYTES // 2, dtype=torch.float32)          # 2x the budget in float32
+    small = torch.randn(1, 5, 8, 8, dtype=torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"canvas": small, "big": big, "x64": torch.ones(3, dtype=torch.float64)})
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("canvas", "big", "x64")}
+    assert a["canvas"].dtype == np.float32 and a["canvas"].shape == (1, 5, 8, 8) and np.array_equal(a["canvas"], small.float().numpy())
+    assert a["big"].dtype == np.float32 and 0 < a["big"].size < big.numel() and np.all(np.diff(a["big"]) >= 0)   # a sorted sample of arange
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 10 ** 6
+    bench.dump_outputs(str(tmp_path / "r"), {"canvas": small}, rank=1, world=2)
+    assert os.listdir(tmp_path / "r") == ["canvas_rank1.npy"]

@@ -631,3 +631,30 @@ def test_bench_multi_rank_branch_dry_run_on_one_gpu():
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["decoded_mp_per_step"] == pytest.approx(71.368704)
     assert d["seam"]["bytes_total_per_step"] == 32 * 5 * 64 * 64 * 4 and d["seam"]["windows_rank0"] == 512 and "dry run" in d["seam"]["backend"]
     assert d["value"] > 0 and d["roofline"]["frac"] > 0
+
+
+def test_bench_plain_run_times_the_steps_only_and_full_adds_the_legs(tmp_path):
+    """bench.py without --full: the timed steps and the line (no kernel profile, latency leg or CPU baseline); --dump-outputs writes the last timed
+    step's tiles.  With --full the extra legs are back in the line, and the same arguments give the same outputs (seeded inputs)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--workload", "tiles", "--tiles-per-step", "2", "--edm-steps", "2", "--steps", "3", "--warmup", "1"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *common, *extra, "--dump-outputs", str(tmp_path / mode)],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[mode] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    p, f = lines["plain"], lines["full"]
+    for d in (p, f):
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "MP/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+        assert abs(d["value"] - d["config"]["decoded_mp_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+    assert "latency_single_tile_ms" not in p and "cpu_baseline" not in p and "all_conv_kernels_ms_per_step" not in p["roofline"]
+    assert p["roofline"]["frac"] > 0
+    assert f["latency_single_tile_ms"] > 0 and f["roofline"]["all_conv_kernels_ms_per_step"] > 0 and "cpu_baseline" not in f
+    a, b = np.load(tmp_path / "plain" / "tiles.npy"), np.load(tmp_path / "full" / "tiles.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 5, 64, 64) and np.isfinite(a).all()
+    assert rel_rms(b, a) < 1e-3
