@@ -13,3 +13,4 @@ from .sampling import sample_decoder_diffusion_tiled, sample_decoder_consistency
 from .noise import gaussian_noise_patch, gaussian_noise_patches, standard_normal, next_seed, _tile_seed  # noqa: F401
 from .world_pipeline import WorldPipeline  # noqa: F401
 from .infinite_tensor import InfiniteTensor, TensorWindow, MemoryTileStore, DeviceTileStore, HDF5TileStore  # noqa: F401
+from .relief import relief_map, get_relief_map  # noqa: F401
