@@ -14,3 +14,5 @@ from .noise import gaussian_noise_patch, gaussian_noise_patches, standard_normal
 from .world_pipeline import WorldPipeline  # noqa: F401
 from .infinite_tensor import InfiniteTensor, TensorWindow, MemoryTileStore, DeviceTileStore, HDF5TileStore  # noqa: F401
 from .relief import relief_map, get_relief_map  # noqa: F401
+from .hydrology import (flow_directions, flow_accumulation_map, flow_indicator, fill_depressions, d8_flow, flow_accumulation,  # noqa: F401
+                        plot_flow_indicator, fill_depressions_priority_flood)
