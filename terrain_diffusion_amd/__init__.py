@@ -16,3 +16,5 @@ from .infinite_tensor import InfiniteTensor, TensorWindow, MemoryTileStore, Devi
 from .relief import relief_map, get_relief_map  # noqa: F401
 from .hydrology import (flow_directions, flow_accumulation_map, flow_indicator, fill_depressions, d8_flow, flow_accumulation,  # noqa: F401
                         plot_flow_indicator, fill_depressions_priority_flood)
+from .minecraft import (get_upsampled, classify_biome, get_terrain, minecraft_terrain, minecraft_payload, noise_planes,  # noqa: F401
+                        parse_minecraft_payload)
