@@ -21,16 +21,18 @@
 //     * online softmax in fp32 with exp2; keys beyond Lk are masked to -inf; O is rescaled per tile.  Two roundings differ from the textbook form
 //       (round 3, "lean softmax"), both inside the bf16-operand error budget and both exercised by tests/test_gpu_attention.py:
 //       (1) scale * log2(e) is folded into Q BEFORE Q is rounded to bf16 (one multiply per score saved): for a scale that is not a power of two
-//           this is one extra bf16 rounding of Q, <= 2^-9 relative per element, the same size as the operand rounding itself;
+//           this is one extra bf16 rounding of Q, <= 2^-8 relative per element (the unit roundoff of bf16, 8 significand bits), the size of the operand rounding itself;
 //       (2) the denominator sums the fp32 probabilities while the numerator contracts their bf16 roundings: numerator and denominator are not
 //           normalised against identical values any more; the mismatch is the mean of the rounding errors of the weights of one query --
-//           unbiased, <= 2^-9 relative and shrinking with the number of keys (measured 1.2-1.5e-3 rel-RMS against a bf16-operand reference
+//           unbiased, <= 2^-8 relative and shrinking with the number of keys (measured 1.2-1.5e-3 rel-RMS against a bf16-operand reference
 //           on every shape of the test, 4096 keys at d = 40 with scale 0.173 included; bound in the test 4e-3).
 //       (3) deferred maximum (round 4, TD_ATTN_THR = 8): the reference point of a query's exponentials follows its running maximum only when
 //           some query of the wave has outgrown its own by more than 2^8; in between the probabilities of a tile are <= 2^8 instead of <= 1
 //           (fp32 accumulators, same bf16 relative precision, numerator and denominator share the reference point).  It removes the rescale
 //           of O -- a dependent, packed-multiply pass in front of the PV MFMAs -- from most tiles: +6 % / +3 % / +8 % at d = 40 / 64 / 128 on
 //           the 4096 x 4096 problem, rel-RMS against the fp64 reference 1.55e-3 -> 1.65e-3 (profiles/r04_attention_mfma_utilisation.txt).
+//     The per-element error bounds that follow from these roundings (u_b = 2^-8 for a bf16 probability, both denominator forms) are derived in tests/_attn_twin.py,
+//     which holds every output element of these kernels to them against a float64 twin.
 // K / V^T rows in LDS are padded to an odd number of 16-byte slots, which makes every 16-lane ds_read_b128 group conflict-free.
 // Consecutive MFMAs go to different accumulators (an instruction between two MFMAs on the SAME accumulator costs ~43 cycles, MI355X_MICROARCH.md).
 #include "conv_common.h"
@@ -544,7 +546,7 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const __bf16* __rest
                 for (int e = 0; e < 8; e += 2) {
                     const float p0 = __builtin_amdgcn_exp2f(s[kb][jj * 8 + e] - m_new);       // inputs <= 0, flushing tiny results to 0 is fine
                     const float p1 = __builtin_amdgcn_exp2f(s[kb][jj * 8 + e + 1] - m_new);
-                    psum_e += p0; psum_o += p1;                                               // fp32 denominator (the numerator rounds to bf16: 2^-9 relative, unbiased)
+                    psum_e += p0; psum_o += p1;                                               // fp32 denominator (the numerator rounds to bf16: 2^-8 relative, unbiased)
                     pb[e] = (__bf16)p0; pb[e + 1] = (__bf16)p1;
                 }
                 pf[kb * 2 + jj] = __builtin_bit_cast(u32x4, pb);

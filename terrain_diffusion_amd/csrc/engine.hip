@@ -976,9 +976,16 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         return TD_OK;
     };
 
-    // bf16 mode: attention blocks run on the MFMA kernel (attn_mfma.hip); its packed operands live in a per-op workspace
+    // bf16 mode: attention blocks run on the MFMA kernel (attn_mfma.hip); its packed operands live in a per-op workspace.  Everything else -- fp16, fp32, and bf16
+    // with option attn_mfma = 0 -- runs the scalar attn_kernel (small_kernels.hip), whose LDS tiles hold 64 tokens: more is refused here, before anything is launched
+    const bool attn_on_mfma = u->dt == TD_DTYPE_BF16 && u->eng->option("attn_mfma", 1) != 0;
+    auto attn_fits = [&](int tokens, const std::string& name) -> int {
+        if (tokens > 64 && !attn_on_mfma)
+            return fail(TD_ERR_UNSUPPORTED, "attention over more than 64 tokens needs bf16 mode with option attn_mfma = 1 (MFMA kernel; the scalar kernel holds 64): " + name);
+        return TD_OK;
+    };
     auto attn_workspace = [&](Op& a) -> int {
-        if (u->dt != TD_DTYPE_BF16 || u->eng->option("attn_mfma", 1) == 0) return TD_OK;
+        if (!attn_on_mfma) return TD_OK;
         size_t qn, kn, vn;
         const size_t tot = attn_workspace_elems(N, a.C / 64, a.tokens, a.tokens, 64, &qn, &kn, &vn);
         void* ws;
@@ -1016,11 +1023,11 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
             if ((rc = conv(b.name + ".conv_res0", {{&xs, b.cout, 9, rs, 2, 1.f}}, h, w, EPI_EMB_SILU, b.cvec_off, nullptr, 0, false, 0.f, false, false, &y1))) return rc;
             if ((rc = conv(b.name + ".conv_res1", {{&y1, b.cout, 9, 0, 0, 1.f}}, h, w, EPI_RESIDUAL, -1, &xs, rs, true, b.attn ? 0.f : 256.f, next_norms && !b.attn, false, &o))) return rc;
             if (b.attn) {
-                if (h * w > 64 && u->dt != TD_DTYPE_BF16) return fail(TD_ERR_UNSUPPORTED, "attention over more than 64 tokens needs bf16 mode (MFMA kernel): " + b.name);
+                if ((rc = attn_fits(h * w, b.name))) return rc;
                 Tensor qkv, att, o2;
                 if ((rc = conv(b.name + ".attn_qkv", {{&o, b.cout, 1, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, false, &qkv))) return rc;
                 if ((rc = new_tensor(b.cout, h, w, false, 0, &att))) return rc;
-                Op a; a.kind = Op::ATTN; a.qkv = qkv.ptr; a.att = att.ptr; a.tokens = h * w; a.C = b.cout; a.label = b.name + ".attn";
+                Op a; a.kind = Op::ATTN; a.qkv = qkv.ptr; a.att = att.ptr; a.tokens = h * w; a.C = b.cout; a.label = b.name + ".attn"; a.out_C = b.cout; a.out_H = h; a.out_W = w;
                 if ((rc = attn_workspace(a))) return rc;
                 pl.ops.push_back(a);
                 if ((rc = conv(b.name + ".attn_proj", {{&att, b.cout, 1, 0, 0, 1.f}}, h, w, EPI_RESIDUAL, -1, &o, 0, false, 256.f, next_norms, false, &o2))) return rc;
@@ -1052,11 +1059,11 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         } else res = &cur;
         if ((rc = conv(b.name + ".conv_res1", s1, h, w, EPI_RESIDUAL, -1, res, b.resample, false, b.attn ? 0.f : 256.f, false, false, &o))) return rc;
         if (b.attn) {
-            if (h * w > 64 && u->dt != TD_DTYPE_BF16) return fail(TD_ERR_UNSUPPORTED, "attention over more than 64 tokens needs bf16 mode (MFMA kernel): " + b.name);
+            if ((rc = attn_fits(h * w, b.name))) return rc;
             Tensor qkv, att, o2;
             if ((rc = conv(b.name + ".attn_qkv", {{&o, b.cout, 1, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, false, &qkv))) return rc;
             if ((rc = new_tensor(b.cout, h, w, false, 0, &att))) return rc;
-            Op a; a.kind = Op::ATTN; a.qkv = qkv.ptr; a.att = att.ptr; a.tokens = h * w; a.C = b.cout; a.label = b.name + ".attn";
+            Op a; a.kind = Op::ATTN; a.qkv = qkv.ptr; a.att = att.ptr; a.tokens = h * w; a.C = b.cout; a.label = b.name + ".attn"; a.out_C = b.cout; a.out_H = h; a.out_W = w;
             if ((rc = attn_workspace(a))) return rc;
             pl.ops.push_back(a);
             if ((rc = conv(b.name + ".attn_proj", {{&att, b.cout, 1, 0, 0, 1.f}}, h, w, EPI_RESIDUAL, -1, &o, 0, false, 256.f, false, false, &o2))) return rc;
@@ -1449,15 +1456,17 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
         return fail(TD_ERR_ARG, "no sumsq for that op");
     }
     for (auto& op : pl->ops) {
-        if (op.kind != Op::CONV || op.label != label) continue;
-        const int C = op.out_C, h = op.out_H, w = op.out_W, cs = op.p.out_cstride;
+        if (op.label != label) continue;
+        // a conv op, or an attention op ("<block>.attn": its NHWC output, channel stride C, in the storage type)
+        const bool is_attn = op.kind == Op::ATTN;
+        const int C = op.out_C, h = op.out_H, w = op.out_W, cs = is_attn ? op.C : op.p.out_cstride;
         dims[0] = n; dims[1] = C; dims[2] = h; dims[3] = w;
         if ((int64_t)n * C * h * w > capacity) return fail(TD_ERR_ARG, "capacity");
         HIP_TRY(hipStreamSynchronize(u->eng->stream));
         const size_t elems = (size_t)n * h * w * cs;
-        const bool f32out = op.p.out_f32 || !u->bf16;
+        const bool f32out = (!is_attn && op.p.out_f32) || !u->bf16;
         std::vector<uint8_t> raw(elems * (f32out ? 4 : 2));
-        HIP_TRY(hipMemcpy(raw.data(), op.p.out, raw.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(raw.data(), is_attn ? op.att : op.p.out, raw.size(), hipMemcpyDeviceToHost));
         for (int i = 0; i < n; ++i)
             for (int c = 0; c < C; ++c)
                 for (int p = 0; p < h * w; ++p) {
@@ -1470,7 +1479,7 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
                 }
         return TD_OK;
     }
-    return fail(TD_ERR_ARG, std::string("no conv op labelled ") + label);
+    return fail(TD_ERR_ARG, std::string("no conv or attention op labelled ") + label);
 }
 
 // ---- schedule: the Karras sigma ladder is computed by the host scheduler with the reference's own fp32 torch ops (bit-exact,

@@ -55,7 +55,9 @@ def test_twin_chained_in_float64_is_the_reference_network(which):
 def test_plan_op_counts():
     assert len(ct.describe(dict(BASE_CONFIG))[0]) == 79
     ops, c_total = ct.describe(tiny_config(64, 2, attn_resolutions=[128]))
-    assert sum(o["label"].endswith(".attn_proj") for o in ops) == sum(o["tier"] == "B" for o in ops) > 0
+    proj = [o for o in ops if o["label"].endswith(".attn_proj")]
+    assert len(proj) > 0 and all(o["segs"][0]["src"] == o["label"][:-5] and o["segs"][0]["xform"] == 0 for o in proj)   # ordinary 1x1 convs of the stored "<block>.attn"
+    assert not any("tier" in o for o in ops)                                                                          # no op with a looser criterion than the others
     assert all(o["K"] == sum(s["C"] * s["taps"] for s in o["segs"]) for o in ops)
 
 

@@ -1,5 +1,5 @@
 """Every fused conv op of the network, element by element, against the float64 twin of the same op on the op's own stored inputs (tests/_conv_twin.py):
-|hip - ref| <= half_ulp_T(ref) + E for EVERY element of every op (tier A; `attn_proj` tier B), and the sum-of-squares planes of every op that writes them
+|hip - ref| <= half_ulp_T(ref) + E for EVERY element of every op (`attn_proj` from the stored attention output, like any 1x1 conv), and the sum-of-squares planes of every op that writes them
 against the float64 sum of squares of the stored output.  One arm per kernel flavour / tile shape / storage type / map shape; each arm asserts from the
 profile labels that the intended flavour really ran, and prints one line: ops, elements, worst (|err| - half_ulp) / E, share of elements whose stored value
 is not RNE_T(ref), wall time.  A failure names the op, the flavour, the worst element and the bounding box of the failing ones."""
