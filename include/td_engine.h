@@ -132,7 +132,9 @@ int td_unet_forward(td_unet* u, int n, int H, int W, const float* x, const float
 /* Test/debug facility: after a td_unet_forward(n,H,W), copies the OUTPUT of the fused conv op `label` (e.g. "enc.512x512_block0.conv_res1",
  * the block output; "<block>.conv_res0" = y1) to host as NCHW fp32.  dims receives (n,C,h,w).  Other labels: "<block>.attn" = the output of the block's
  * attention op (what "<block>.attn_proj" reads), returned like a conv output; "sumsq:<conv label>" = that op's sum-of-squares planes (parts,n,h,w);
- * "@emb" / "@cvec" = the embedding / modulation rows (n,width,1,1). */
+ * "@emb" / "@cvec" = the first n embedding / modulation rows (n,width,1,1); "@emb:rows" / "@cvec:rows" = EVERY row the last call on this plan computed,
+ * (rows,width,1,1), row = step * n + tile: n_steps * n rows after a sampler call, n after a forward with one t, and after a forward with differing t the
+ * n * n cross product with the rows (i,i) the forward uses copied over rows 1 .. n-1. */
 int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, float* out_host, int64_t capacity, int32_t dims[4]);
 
 /* ---- portable noise (terrain_diffusion/inference/portable_rng.py:22-89, world_pipeline.py:58-115) ---------- */

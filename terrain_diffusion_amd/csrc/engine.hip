@@ -315,7 +315,8 @@ struct Plan {
     float* partial = nullptr;
     // sampler state
     Buf x, m1, m2, xt, cond, emb, cvec, tsteps;
-    int cvec_rows = 0;
+    int cvec_rows = 0;         // rows emb / cvec are allocated for
+    int cvec_written = 0;      // rows the last compute_cvecs wrote (read-back labels "@emb:rows" / "@cvec:rows")
     // graph cache for the EDM loop
     hipGraphExec_t graph = nullptr;
     std::vector<float> graph_sigmas;
@@ -1160,6 +1161,7 @@ static int compute_cvecs(td_unet* u, Plan& pl, const std::vector<float>& t_steps
     hipLaunchKernelGGL(cvec_norm_kernel, dim3(rows, u->n_blocks), dim3(256), 0, st, (float*)pl.cvec->p, (const int*)u->d_blk_coff->p,
                        (const int*)u->d_blk_cout->p, u->c_total);
     HIP_TRY(hipGetLastError());
+    pl.cvec_written = rows;
     return TD_OK;
 }
 
@@ -1440,6 +1442,17 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
         if ((int64_t)n * width > capacity) return fail(TD_ERR_ARG, "capacity");
         HIP_TRY(hipStreamSynchronize(u->eng->stream));
         HIP_TRY(hipMemcpy(out_host, is_emb ? pl->emb->p : pl->cvec->p, (size_t)n * width * 4, hipMemcpyDeviceToHost));
+        return TD_OK;
+    }
+    if (!strcmp(label, "@emb:rows") || !strcmp(label, "@cvec:rows")) {
+        // every (step, tile) row the last compute_cvecs on this plan wrote, not only the first n
+        const bool is_emb = !strcmp(label, "@emb:rows");
+        const int width = is_emb ? u->emb_ch : u->c_total, rows = pl->cvec_written;
+        if (rows < 1 || !pl->emb) return fail(TD_ERR_STATE, "no embedding rows on this plan yet: run a forward or a sampler call first");
+        dims[0] = rows; dims[1] = width; dims[2] = 1; dims[3] = 1;
+        if ((int64_t)rows * width > capacity) return fail(TD_ERR_ARG, "capacity");
+        HIP_TRY(hipStreamSynchronize(u->eng->stream));
+        HIP_TRY(hipMemcpy(out_host, is_emb ? pl->emb->p : pl->cvec->p, (size_t)rows * width * 4, hipMemcpyDeviceToHost));
         return TD_OK;
     }
     if (!strncmp(label, "sumsq:", 6)) {
