@@ -83,7 +83,8 @@ int td_engine_set_stream(td_engine* e, void* hip_stream);
  *   "graph"=0/1 (hipGraph capture of the sampler loops), "profile"=0/1, "async"=0/1 (see td_engine_set_stream),
  *   "batch_invariant"=0/1 (a window's result does not depend on the batch / GPU it rides in: no split-K, LDS-DMA conv flavour pinned),
  *   "solver_order"=1/2/3 and "lower_order_final"=0/1 (EDMDPMSolverMultistepScheduler.config), "fuse_solver"=0/1 (solver update in the
- *   output conv's epilogue), "dual_stream"=0/1 (default 1) + "dual_stream_min_batch" (default 32: batches at least that large run as two concurrent half-batch lanes), "plan_cache_mb", "plan_cache_max".
+ *   output conv's epilogue), "dual_stream"=0/1 (default 1) + "dual_stream_min_batch" (default 32: batches at least that large run as two concurrent half-batch lanes), "plan_cache_mb", "plan_cache_max",
+ *   "sampler_stop_after"=-1/k (test read-back, default -1 = off: td_sample_edm* enqueue only the first min(k, n_steps) steps of the n_steps-step run).
  * Plan builder (speed only; every one is part of the plan-cache key):
  *   "glds", "glds_min_wgs", "glds_bn64", "glds_round_aware", "glds_small_max_groups", "glds_dma1x1", "glds_tiny", "bn128_min_wgs",
  *   "splitk", "splitk_target_wgs", "splitk_weighted", "glds_splitk", "glds_splitk_from_groups", "glds_splitk_max", "glds_splitk_min_groups",
@@ -134,7 +135,9 @@ int td_unet_forward(td_unet* u, int n, int H, int W, const float* x, const float
  * attention op (what "<block>.attn_proj" reads), returned like a conv output; "sumsq:<conv label>" = that op's sum-of-squares planes (parts,n,h,w);
  * "@emb" / "@cvec" = the first n embedding / modulation rows (n,width,1,1); "@emb:rows" / "@cvec:rows" = EVERY row the last call on this plan computed,
  * (rows,width,1,1), row = step * n + tile: n_steps * n rows after a sampler call, n after a forward with one t, and after a forward with differing t the
- * n * n cross product with the rows (i,i) the forward uses copied over rows 1 .. n-1. */
+ * n * n cross product with the rows (i,i) the forward uses copied over rows 1 .. n-1.  Sampler state as the last call on the plan left it: "@x" / "@m1" /
+ * "@m2" / "@xt" = the sample, the two solver histories and the consistency sampler's x_t, planar fp32 (n,C_out,H,W); "@xin" = the NHWC model input widened
+ * to fp32, (n,chunk,H,W) with every channel of the K chunk (sample, conditioning image, ones channel, zero padding). */
 int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, float* out_host, int64_t capacity, int32_t dims[4]);
 
 /* ---- portable noise (terrain_diffusion/inference/portable_rng.py:22-89, world_pipeline.py:58-115) ---------- */
@@ -148,6 +151,10 @@ int td_noise_patches(td_engine* e, uint64_t base_seed, int n_windows, const int6
  * the reference computes with torch CPU ops; the host scheduler (terrain_diffusion_amd/scheduler.py) repeats those ops and is bit-exact.
  * A C restatement with libm powf differs in the last bits (2e-6), so round 1's td_schedule_karras was removed rather than ship an
  * export that disagrees with the product path.  The samplers below take the sigma ladder from the caller. */
+
+/* The solver coefficients td_sample_edm* derive from a sigma ladder (the sampler's own function, for tests): out = n_steps rows of 13 floats
+ * (c_skip, c_out, a, b0, inv_r0, inv_r1, f01, inv_r01, c1, c2, c_in_next, order, last); host arithmetic only, no engine needed. */
+int td_dpm_coefs(const float* sigmas_host, int n_steps, float sigma_data, int solver_order, int lower_order_final, float* out);
 
 /* ---- samplers ---------------------------------------------------------------------------------------------
  * Inner loop of sample_base_diffusion (terrain_diffusion/training/evaluation/sample_diffusion_base.py:147-162)

@@ -46,6 +46,7 @@ _SIGS = {
     "td_unet_cond_row_len": (C.c_int, [_P]),
     "td_unet_forward": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "td_unet_read_activation": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int32 * 4)]),
+    "td_dpm_coefs": (C.c_int, [_P, C.c_int, C.c_float, C.c_int, C.c_int, _P]),
     "td_tile_seed": (C.c_uint64, [C.c_uint64, C.c_int64, C.c_int64]),
     "td_standard_normal": (C.c_int, [_P, C.c_uint64, C.c_int64, _P]),
     "td_noise_patches": (C.c_int, [_P, C.c_uint64, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),

@@ -165,7 +165,7 @@ __device__ __forceinline__ float epilogue4(const ConvParams& p, int n, int y, in
                 p.dpm_x[xi] = xn;
                 if (p.dpm_m2) p.dpm_m2[xi] = m1v;   // history shifts: m2 <- m1 <- m0
                 p.dpm_m1[xi] = m0;
-                if (!k.last) ((T*)p.dpm_xin)[(size_t)pix * p.dpm_xin_cstride + co + q] = (T)(xn * k.c_in_next);
+                if (!k.last) ((T*)p.dpm_xin)[(size_t)pix * p.dpm_xin_cstride + co + q] = mul_then_cast<T>(xn, k.c_in_next);
             }
         return 0.f;
     }

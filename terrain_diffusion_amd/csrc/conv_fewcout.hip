@@ -9,7 +9,8 @@
 //
 // Same parameter block and packed weight slab ([K-step][cout][128 B], slot (piece ^ TD_SWZ(cout))) as the other flavours.  fp32 accumulation in another
 // order than theirs (two chains of channel-pair dot products per cout): results agree to fp32 rounding of the sums, not bit for bit; the flavour of a
-// launch depends on its shape only.  One 3x3 segment, no transform at staging, no resampling, EPI_PLAIN, fp32 output rows of p.out_cstride floats.
+// launch depends on its shape only.  One 3x3 segment, no transform at staging, no resampling, fp32 output rows of p.out_cstride floats (EPI_PLAIN), or
+// the sampler's solver step on that same fp32 sum (EPI_DPM_STEP, the shared epilogue4): a fused step has the bits of this kernel followed by dpm_step_kernel.
 #include "conv_common.h"
 
 namespace td {
@@ -86,6 +87,13 @@ __global__ __launch_bounds__(256) void conv_fewcout_kernel(const ConvParams p) {
     }
     const int y = y0 + ly, x = x0 + lx;
     if (y < H && x < W) {
+        if (p.epi == EPI_DPM_STEP) {   // the sampler's solver step on F = the very sum the plain path stores: epilogue4's arithmetic, couts [0, Cout) of this pixel
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < CO; ++c) v[c] = acc[c][0] + acc[c][1];
+            (void)epilogue4<T>(p, n0, y, x, 0, v, 0.f, v);
+            return;
+        }
         float* o = (float*)p.out + (size_t)((n0 * H + y) * W + x) * p.out_cstride;
 #pragma unroll
         for (int c = 0; c < CO; ++c) if (c < p.Cout) o[c] = acc[c][0] + acc[c][1];
@@ -105,7 +113,8 @@ static hipError_t launch_fewcout_cfg(const ConvParams& p, hipStream_t st) {
 hipError_t launch_conv_fewcout(const ConvParams& p, int dtype, hipStream_t st) {
     if (p.nseg != 1 || p.seg[0].taps != 9 || p.seg[0].xform != 0 || p.seg[0].resample != 0 || p.seg[0].Hs != p.H || p.seg[0].Ws != p.W || (p.seg[0].C & 63) || p.seg[0].C < 64)
         return hipErrorInvalidValue;
-    if (p.epi != EPI_PLAIN || !p.out_f32 || p.ksplit != 1 || p.res || p.out2 || p.out_sumsq || p.clip > 0.f || p.Cout < 1 || p.Cout > 4 || p.out_cstride < p.Cout)
+    if (p.epi == EPI_DPM_STEP && (!p.dpm_x || !p.dpm_m1 || !p.dpm_xin || p.dpm_xin_cstride < p.Cout || (p.dpm_k.order == 3 && !p.dpm_m2))) return hipErrorInvalidValue;
+    if ((p.epi != EPI_PLAIN && p.epi != EPI_DPM_STEP) || !p.out_f32 || p.ksplit != 1 || p.res || p.out2 || p.out_sumsq || p.clip > 0.f || p.Cout < 1 || p.Cout > 4 || p.out_cstride < p.Cout)
         return hipErrorInvalidValue;
     if (p.tiles_x != (p.W + 15) / 16 || p.tiles_y != (p.H + 15) / 16) return hipErrorInvalidValue;
     const int co = p.Cout <= 1 ? 1 : p.Cout <= 2 ? 2 : 4;

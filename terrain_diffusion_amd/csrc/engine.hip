@@ -324,6 +324,7 @@ struct Plan {
     int graph_solver_order = 0;
     int graph_lof = -1;        // engine option "lower_order_final" the graph was captured under
     int graph_fuse = -1;       // engine option "fuse_solver" the graph was captured under
+    int graph_stop = -2;       // engine option "sampler_stop_after" the graph was captured under
     const void* graph_guide = nullptr;       // guide plan / its modulation buffer / scale the captured graph was built with (autoguidance)
     const void* graph_guide_cvec = nullptr;
     float graph_gscale = 0.f;
@@ -937,7 +938,7 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         // Few-cout flavour (conv_fewcout.hip, round 6): an fp32-output 3x3 conv with <= 4 real couts (the decoder model's 64 -> 1 output conv) does its
         // multiply-adds on the VALU, one pixel per thread, instead of a 64-cout MFMA tile for one cout.  Maps of >= 128 x 128 pixels (a rule of the shape
         // only: also legal in batch_invariant mode); option "fewcout" = 0 keeps the MFMA tile.  If the sampler later fuses its solver step into this conv
-        // (EPI_DPM_STEP), the launch falls back to conv_glds's 128-pixel tile.
+        // (EPI_DPM_STEP), the same kernel runs the step in its epilogue: fused and unfused runs of the decoder model have the same bits.
         if (u->eng->option("fewcout", 1) != 0 && (u->dt == 1 || u->dt == 2) && out_f32 && epi == EPI_PLAIN && cw.cout <= 4 && segs.size() == 1 && segs[0].taps == 9 &&
             segs[0].xform == 0 && p.seg[0].resample == 0 && p.seg[0].Hs == h && p.seg[0].Ws == w && !res && clip <= 0.f && (int64_t)h * w >= 128 * 128 && w >= 16) {
             op.flavor = 6; op.bn = 64; op.glds_variant = 0; op.narrow = false;
@@ -1216,10 +1217,7 @@ static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = null
             p.epi = EPI_DPM_STEP; p.dpm_x = (float*)pl.x->p; p.dpm_m1 = (float*)pl.m1->p; p.dpm_m2 = u->eng->option("solver_order", 2) == 3 ? (float*)pl.m2->p : nullptr; p.dpm_xin = pl.xin; p.dpm_xin_cstride = u->chunk; p.dpm_k = *fuse;
         }
         mark();
-        if (op.flavor == 6 && p.epi != EPI_PLAIN) {   // the solver step was fused into this launch: the MFMA flavour has that epilogue
-            p.tiles_x = (p.W + 15) / 16; p.tiles_y = (p.H + 7) / 8; p.img_groups = p.N; p.n_ntiles = p.CoutPad / 64;
-        }
-        hipError_t e = op.flavor == 6 ? (p.epi == EPI_PLAIN ? launch_conv_fewcout(p, u->dt, st) : launch_conv_glds(p, u->dt, false, 64, 1, st))
+        hipError_t e = op.flavor == 6 ? launch_conv_fewcout(p, u->dt, st)   // with the solver step fused too: the same sums as the plain launch, then epilogue4's step
                        : op.flavor == 5 ? launch_conv_s16(p, u->dt, op.narrow, st)
                        : op.flavor == 4 ? launch_conv_sb(p, u->dt, op.narrow, op.sb_mt, op.sb_nt, st)
                        : op.flavor == 2 ? (op.glds_variant == 3 ? launch_conv_glds_wide(p, u->dt, op.bn, st) : launch_conv_glds(p, u->dt, op.narrow, op.bn, op.glds_variant, st))
@@ -1300,7 +1298,7 @@ int td_engine_set_stream(td_engine* e, void* hip_stream) {
 // read -- silently losing, e.g., the bit-identity of sharded runs.
 static const char* const kKnownOptions[] = {
     // behaviour
-    "async", "batch_invariant", "fuse_solver", "graph", "lower_order_final", "profile", "solver_order", "dual_stream", "dual_stream_min_batch",
+    "async", "batch_invariant", "fuse_solver", "graph", "lower_order_final", "profile", "solver_order", "dual_stream", "dual_stream_min_batch", "sampler_stop_after",
     "plan_cache_mb", "plan_cache_max",
     // plan builder (speed only, or test hooks that force a tile shape; all part of the plan-cache key)
     "attn_mfma", "bn128_min_wgs", "glds", "glds_bn", "glds_bn64", "glds_dma1x1", "glds_min_wgs", "glds_round_aware", "glds_small_max_groups",
@@ -1455,6 +1453,37 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
         HIP_TRY(hipMemcpy(out_host, is_emb ? pl->emb->p : pl->cvec->p, (size_t)rows * width * 4, hipMemcpyDeviceToHost));
         return TD_OK;
     }
+    if (!strcmp(label, "@x") || !strcmp(label, "@m1") || !strcmp(label, "@m2") || !strcmp(label, "@xt")) {
+        // sampler state of this plan as the last call left it: planar fp32 [n][C_out][H][W]
+        const int C = u->cfg.out_channels;
+        const Buf& b = !strcmp(label, "@x") ? pl->x : !strcmp(label, "@m1") ? pl->m1 : !strcmp(label, "@m2") ? pl->m2 : pl->xt;
+        dims[0] = n; dims[1] = C; dims[2] = H; dims[3] = W;
+        if ((int64_t)n * C * H * W > capacity) return fail(TD_ERR_ARG, "capacity");
+        HIP_TRY(hipStreamSynchronize(u->eng->stream));
+        HIP_TRY(hipMemcpy(out_host, b->p, (size_t)n * C * H * W * 4, hipMemcpyDeviceToHost));
+        return TD_OK;
+    }
+    if (!strcmp(label, "@xin")) {
+        // the NHWC model input, every channel of the K chunk (sample, conditioning image, ones channel, padding), widened to fp32
+        const int cs = u->chunk;
+        const size_t HW = (size_t)H * W, elems = (size_t)n * HW * cs;
+        dims[0] = n; dims[1] = cs; dims[2] = H; dims[3] = W;
+        if ((int64_t)elems > capacity) return fail(TD_ERR_ARG, "capacity");
+        HIP_TRY(hipStreamSynchronize(u->eng->stream));
+        std::vector<uint8_t> raw(elems * (u->bf16 ? 2 : 4));
+        HIP_TRY(hipMemcpy(raw.data(), pl->xin, raw.size(), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i)
+            for (int c = 0; c < cs; ++c)
+                for (size_t p = 0; p < HW; ++p) {
+                    const size_t src = ((size_t)i * HW + p) * cs + c;
+                    float v;
+                    if (!u->bf16) v = ((const float*)raw.data())[src];
+                    else if (u->dt == TD_DTYPE_F16) { _Float16 h; memcpy(&h, (const uint16_t*)raw.data() + src, 2); v = (float)h; }
+                    else { uint32_t b = (uint32_t)((const uint16_t*)raw.data())[src] << 16; memcpy(&v, &b, 4); }
+                    out_host[((size_t)i * cs + c) * HW + p] = v;
+                }
+        return TD_OK;
+    }
     if (!strncmp(label, "sumsq:", 6)) {
         for (auto& op : pl->ops) {
             if (op.kind != Op::CONV || op.label != label + 6 || !op.p.out_sumsq) continue;
@@ -1535,6 +1564,20 @@ static void dpm_coefs(const float* sig, int n_steps, float sigma_data, int solve
     }
 }
 
+// The table above as the sampler uses it, for inspection: n_steps rows of 13 floats, the fields of SchedCoef in declaration order (order / last as floats).
+int td_dpm_coefs(const float* sigmas_host, int n_steps, float sigma_data, int solver_order, int lower_order_final, float* out) {
+    if (!sigmas_host || !out || n_steps < 1) return fail(TD_ERR_ARG, "td_dpm_coefs: null argument or n_steps < 1");
+    if (solver_order < 1 || solver_order > 3) return fail(TD_ERR_ARG, "solver_order must be 1, 2 or 3");
+    std::vector<SchedCoef> ks;
+    dpm_coefs(sigmas_host, n_steps, sigma_data, solver_order, lower_order_final != 0, ks);
+    for (int i = 0; i < n_steps; ++i) {
+        const SchedCoef& k = ks[i];
+        const float row[13] = {k.c_skip, k.c_out, k.a, k.b0, k.inv_r0, k.inv_r1, k.f01, k.inv_r01, k.c1, k.c2, k.c_in_next, (float)k.order, (float)k.last};
+        memcpy(out + (size_t)i * 13, row, sizeof row);
+    }
+    return TD_OK;
+}
+
 // writes the conditioning-image channels [Cs, Cs+cimg) of the NHWC model input (constant over the solver steps)
 static int stage_cond_img(td_unet* u, Plan& pl, int n, int HW, const float* cond_img, int cimg, int Cs, std::vector<Buf>& hold) {
     if (cimg == 0) return TD_OK;
@@ -1590,6 +1633,15 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
     const bool lof = e->option("lower_order_final", 1) != 0;
     dpm_coefs(sigmas_host, n_steps, sigma_data, solver_order, lof, ks);
     const float c_in0 = 1.f / sqrtf(sigmas_host[0] * sigmas_host[0] + sigma_data * sigma_data);
+    // option "sampler_stop_after" = k >= 0 (test read-back): the table is that of the n_steps-step run, only its first k steps are enqueued, and the
+    // solver history starts from zeros, so that "@m1" / "@m2" after the call depend on this call alone (a full run never reads what an earlier call
+    // left there: the first step ignores m1, and m2 is overwritten twice before the first third-order step reads it)
+    const int stop_after = (int)e->option("sampler_stop_after", -1);
+    const int n_run = stop_after >= 0 ? std::min(stop_after, n_steps) : n_steps;
+    if (stop_after >= 0) {
+        HIP_TRY(hipMemsetAsync(pl->m1->p, 0, xbytes, st));
+        HIP_TRY(hipMemsetAsync(pl->m2->p, 0, xbytes, st));
+    }
 
     auto enqueue = [&]() -> int {
         TD_DISPATCH_T(u, hipLaunchKernelGGL(prep_input_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)pl->x->p, (T_*)pl->xin, n, C, HW, u->chunk, c_in0, Cin));
@@ -1601,7 +1653,7 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
         // epilogue of the U-Net's output conv (option "fuse_solver", default on; bit-identical to the separate kernel: same arithmetic on the same
         // fp32 F); with autoguidance the update needs BOTH models' outputs and stays a kernel of its own.
         const bool fuse = !gpl && e->option("fuse_solver", 1) != 0 && pl->ops.back().kind == Op::CONV && pl->ops.back().p.epi == EPI_PLAIN && pl->ops.back().p.out_f32;
-        for (int i = 0; i < n_steps; ++i) {
+        for (int i = 0; i < n_run; ++i) {
             int r = run_unet(u, *pl, i, fuse ? &ks[i] : nullptr);
             if (r) return r;
             if (fuse) continue;
@@ -1618,7 +1670,8 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
         // the guide's plan can be evicted / its buffers re-allocated independently of this plan: key the graph on them too
         const void* gkey = gpl ? (const void*)gpl->cvec->p : nullptr;
         if (!pl->graph || pl->graph_sigmas != sg || pl->graph_sigma_data != sigma_data || pl->graph_solver_order != solver_order || pl->graph_lof != (int)lof ||
-            pl->graph_guide != (const void*)gpl || pl->graph_guide_cvec != gkey || pl->graph_gscale != gscale || pl->graph_fuse != (int)e->option("fuse_solver", 1)) {
+            pl->graph_guide != (const void*)gpl || pl->graph_guide_cvec != gkey || pl->graph_gscale != gscale || pl->graph_fuse != (int)e->option("fuse_solver", 1) ||
+            pl->graph_stop != stop_after) {
             pl->drop_graph();
             hipGraph_t g = nullptr;
             HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -1630,6 +1683,7 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
             (void)hipGraphDestroy(g);
             if (ie != hipSuccess) { pl->graph = nullptr; return fail(TD_ERR_HIP, std::string("graph instantiate: ") + hipGetErrorString(ie)); }
             pl->graph_sigmas = sg; pl->graph_sigma_data = sigma_data; pl->graph_solver_order = solver_order; pl->graph_lof = (int)lof; pl->graph_fuse = (int)e->option("fuse_solver", 1);
+            pl->graph_stop = stop_after;
             pl->graph_guide = gpl; pl->graph_guide_cvec = gkey; pl->graph_gscale = gscale;
         }
         HIP_TRY(hipGraphLaunch(pl->graph, st));

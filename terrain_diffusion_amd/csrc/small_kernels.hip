@@ -243,7 +243,7 @@ __global__ void prep_input_kernel(const float* __restrict__ x, T* __restrict__ x
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)N * HW) return;
     int n = (int)(i / HW), p = (int)(i % HW);
-    for (int c = 0; c < C; ++c) xin[i * cstride + c] = (T)(x[((size_t)n * C + c) * HW + p] * scale);
+    for (int c = 0; c < C; ++c) xin[i * cstride + c] = mul_then_cast<T>(x[((size_t)n * C + c) * HW + p], scale);
     xin[i * cstride + ones_idx] = (T)1.f;
 }
 // conditioning-image channels of the model input (constant over the solver steps): xin[.., c0 + c] = img[n][c][p]
@@ -284,8 +284,9 @@ __global__ void dpm_step_kernel(float* __restrict__ x, float* __restrict__ m1, c
         if (m2) m2[xi] = m1v;   // third-order solver: history shifts m2 <- m1 <- m0
         m1[xi] = m0;
         if (!k.last) {
-            xin[i * cstride + c] = (T)(xn * k.c_in_next);
-            if (xin2) xin2[i * cstride + c] = (T)(xn * k.c_in_next);  // the guide model's input buffer
+            const T xs_next = mul_then_cast<T>(xn, k.c_in_next);
+            xin[i * cstride + c] = xs_next;
+            if (xin2) xin2[i * cstride + c] = xs_next;  // the guide model's input buffer
         }
     }
 }

@@ -46,6 +46,16 @@ __device__ __forceinline__ void dpm_update(const SchedCoef& k, float xs, float f
     }
 }
 
+// a * b rounded to fp32 and THEN to the storage type, as the reference does (an fp32 product, then the cast).  Left to itself the compiler fuses the multiply into the
+// fp16 conversion (v_fma_mixlo_f16: ONE rounding of the exact product), which differs from the spelled arithmetic wherever the fp32 product lands on an fp16 tie
+// (found on the MI355X by tests/test_sampler_ops_gpu.py: 1 element in ~10^4 of the fp16 model input, one fp16 ulp).  The empty asm keeps the product in a register.
+template <typename T>
+__device__ __forceinline__ T mul_then_cast(float a, float b) {
+    float p = a * b;
+    asm("" : "+v"(p));
+    return (T)p;
+}
+
 enum { EPI_PLAIN = 0, EPI_EMB_SILU = 1, EPI_RESIDUAL = 2, EPI_DPM_STEP = 3 };
 
 struct ConvParams {

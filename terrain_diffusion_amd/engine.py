@@ -128,6 +128,15 @@ def get_engine(device=None) -> Engine:
     return _engines[idx]
 
 
+def dpm_coefs(sigmas, sigma_data, solver_order=2, lower_order_final=True):
+    """The solver coefficients the EDM samplers derive from a sigma ladder (td_dpm_coefs: the sampler's own host function, no GPU needed):
+    (n_steps, 13) float32, columns c_skip, c_out, a, b0, inv_r0, inv_r1, f01, inv_r01, c1, c2, c_in_next, order, last."""
+    s = np.ascontiguousarray(np.asarray(sigmas, dtype=np.float32).reshape(-1))
+    out = np.zeros((s.size - 1, 13), np.float32)
+    check(lib().td_dpm_coefs(C.c_void_p(s.ctypes.data), s.size - 1, float(sigma_data), int(solver_order), int(bool(lower_order_final)), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 _SHARED_STREAM = {}   # device index -> raw handle of the caller stream the engine currently launches on (Engine.set_stream)
 
 

@@ -7,14 +7,15 @@ cd /tmp && export TMPDIR=/tmp
 # ONE sampler lane (--engine-opts dual_stream=0): per-kernel durations and per-dispatch counters are only meaningful when kernels do not overlap; the
 # engine's default (two half-batch lanes, round 6) is what the bench LINE times, its `roofline.single_lane` leg is what these files reproduce
 BENCH="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-profile --no-latency --engine-opts dual_stream=0"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/kt.err
+# a pass that fails, faults or runs into its time limit ends the collection: nothing more is started on the GPU after it
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/kt.err || { echo "kernel-trace pass failed: $?"; tail -5 $OUT/kt.err; exit 1; }
 for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VALU_MFMA_MOPS_BF16"; do
   tag=$(echo $c | cut -d' ' -f1)
-  timeout 900 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$tag -- $BENCH > $OUT/pmc_$tag.log 2>&1
+  timeout -k 10 900 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$tag -- $BENCH > $OUT/pmc_$tag.log 2>&1 || { echo "pmc pass $tag failed: $?"; tail -5 $OUT/pmc_$tag.log; exit 1; }
 done
 B1="python $R/bench.py --workload tiles --tiles-per-step 1 --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-profile --no-latency"
 for c in "FETCH_SIZE" "WRITE_SIZE"; do
-  timeout 600 rocprofv3 --pmc $c --output-format csv -d $OUT/b1pmc_$c -- $B1 > $OUT/b1pmc_$c.log 2>&1
+  timeout -k 10 600 rocprofv3 --pmc $c --output-format csv -d $OUT/b1pmc_$c -- $B1 > $OUT/b1pmc_$c.log 2>&1 || { echo "batch-1 pmc pass $c failed: $?"; tail -5 $OUT/b1pmc_$c.log; exit 1; }
 done
 python3 - <<'PY'
 import csv, glob, os, json, collections
