@@ -18,3 +18,5 @@ from .hydrology import (flow_directions, flow_accumulation_map, flow_indicator, 
                         plot_flow_indicator, fill_depressions_priority_flood)
 from .minecraft import (get_upsampled, classify_biome, get_terrain, minecraft_terrain, minecraft_payload, noise_planes,  # noqa: F401
                         parse_minecraft_payload)
+from .explorer import (coarse_channels, colorize, relief_rgba8, raw_tile, land_tiles, coarse_image, coarse_stats, coarse_data,  # noqa: F401
+                       detail_image, detail_raw, sample_land_tiles, get_coarse_climate_info, png_bytes)
