@@ -36,7 +36,8 @@ def cfg_mix(uncond, cond, guidance_scale):
 
 def ddim_step(latent, eps, a_t, a_prev):
     """eta = 0: x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t);  x_prev = sqrt(a_prev) x0 + sqrt(1 - a_prev) eps   (float32 like the fp32 pipeline)"""
-    latent, eps = np.asarray(latent, np.float32), np.asarray(eps, np.float32)
+    dt = np.float64 if np.asarray(latent).dtype == np.float64 else np.float32      # float64 operands stay float64 (the scalars are fp32 values either way)
+    latent, eps = np.asarray(latent, dt), np.asarray(eps, dt)
     x0 = (latent - np.float32((1.0 - a_t) ** 0.5) * eps) / np.float32(a_t ** 0.5)
     return np.float32(a_prev ** 0.5) * x0 + np.float32((1.0 - a_prev) ** 0.5) * eps
 

@@ -45,10 +45,22 @@ def standard_normal(seed, size, dtype=np.float32, device="cuda", as_torch=False)
     return out if as_torch else out.cpu().numpy().astype(dtype, copy=False)
 
 
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def check_origins(org, h, w):
+    """td_noise_patches takes int64 origins but narrows them to int, and noise_gather_kernel forms origin + y in int: a window whose coordinates leave int32 would
+    wrap there (for a power-of-two tile the wrap happens to cancel in the tile arithmetic, for any other tile it cannot).  Refused here, before the engine is reached."""
+    org = np.asarray(org, dtype=np.int64).reshape(-1, 2)
+    if org.size and (org.min() < INT32_MIN or int(org[:, 0].max()) + h - 1 > INT32_MAX or int(org[:, 1].max()) + w - 1 > INT32_MAX):
+        raise ValueError(f"noise window outside int32 coordinates: origins span {org.min(0).tolist()} .. {org.max(0).tolist()}, window {h} x {w}")
+
+
 def gaussian_noise_patches(base_seed, origins, h, w, channels=1, tile_h=256, tile_w=256, scale=1.0, device="cuda"):
     """Batched gaussian_noise_patch: origins = [(y0, x0), ...] -> device tensor (n, channels, h, w)."""
-    eng = get_engine(device)
     org = np.ascontiguousarray(np.asarray(origins, dtype=np.int64).reshape(-1, 2))
+    check_origins(org, h, w)
+    eng = get_engine(device)
     out = torch.empty((len(org), channels, h, w), dtype=torch.float32, device=torch.device("cuda", eng.device_id))
     check(lib().td_noise_patches(eng._h, int(base_seed) & M64, len(org), C.c_void_p(org.ctypes.data), h, w, channels, tile_h, tile_w, float(scale), ptr(out)))
     return out
