@@ -6,7 +6,40 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libtd_engine.so")
+
+
+class TdError(RuntimeError):
+    pass
+
+
+class Library:
+    """One ctypes library of the package: loaded on first use, with restype / argtypes set for every entry of `sigs` ({name: (restype, argtypes)};
+    a name the library lacks raises AttributeError).  `last_error` names its const char* f(void) entry point, `label` is what messages call it."""
+
+    def __init__(self, file_name, sigs, last_error, label, missing="There is no CPU fallback."):
+        self.path = os.path.join(_HERE, file_name)
+        self.sigs, self.last_error, self.label, self.missing = sigs, last_error, label, missing
+        self.handle = None
+
+    def lib(self):
+        """The loaded library; raises if it has not been built."""
+        if self.handle is None:
+            if not os.path.exists(self.path):
+                raise TdError(f"{self.path} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). {self.missing}")
+            l = C.CDLL(self.path)
+            for name, (res, args) in self.sigs.items():
+                fn = getattr(l, name)
+                fn.restype = res
+                fn.argtypes = args
+            self.handle = l
+        return self.handle
+
+    def error_text(self):
+        return getattr(self.lib(), self.last_error)().decode()
+
+    def check(self, rc):
+        if rc != 0:
+            raise TdError(f"{self.label} error {rc}: {self.error_text()}")
 
 
 class UnetConfig(C.Structure):
@@ -16,10 +49,6 @@ class UnetConfig(C.Structure):
                 ("attn_resolutions", C.c_int32 * 8), ("midblock_attention", C.c_int32), ("concat_balance", C.c_float),
                 ("noise_emb_dims", C.c_int32), ("emb_channels", C.c_int32), ("n_cond", C.c_int32),
                 ("cond_type", C.c_int32 * 8), ("cond_dims", C.c_int32 * 8), ("cond_weights", C.c_float * 8)]
-
-
-class TdError(RuntimeError):
-    pass
 
 
 _P = C.c_void_p
@@ -69,25 +98,5 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS)
 
-_lib = None
-
-
-def lib():
-    """Loads the HIP engine; raises if it has not been built (python __graft_entry__.py build)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TdError(f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
-                          "There is no CPU fallback.")
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(l, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise TdError(f"td_engine error {rc}: {lib().td_last_error().decode()}")
+_LIB = Library("libtd_engine.so", _SIGS, "td_last_error", "td_engine")
+LIB_PATH, lib, check = _LIB.path, _LIB.lib, _LIB.check

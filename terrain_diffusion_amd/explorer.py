@@ -18,7 +18,6 @@ image without matplotlib or PIL.  There is no CPU fallback.
 """
 import ctypes as C
 import functools
-import os
 import random
 import struct
 import zlib
@@ -27,10 +26,10 @@ import numpy as np
 import torch
 
 from . import relief as _relief
-from ._lib import TdError
-from .engine import _SHARED_STREAM, get_engine
+from ._lib import Library
+from ._plumbing import MAX_PIXELS, MAX_SIDE, call, engine_for as _engine_for, f32 as _f32, hw, shape as _shape  # noqa: F401
+from .engine import get_engine
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtd_explorer.so")
 _P = C.c_void_p
 _SIGS = {
     "td_explorer_last_error": (C.c_char_p, []),
@@ -42,54 +41,19 @@ _SIGS = {
     "td_explorer_land_tiles": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, C.c_int]),
 }
 EXPORTS = tuple(_SIGS)
-MAX_SIDE = 1 << 16          # per call: 1 <= H, W <= 2^16 ...
-MAX_PIXELS = 1 << 26        # ... and H * W <= 2^26 pixels (include/td_explorer.h)
 MAX_CHANNELS = 8
 MAX_FILTERS = 8
 MAX_HALF = 2047
 CHANNEL_NAMES = ["Elev", "p5", "Temp", "T std", "Precip", "Precip CV"]
 FILTERABLE = (0, 2, 3, 4, 5)   # server.py: p5 (channel 1) cannot be filtered on
 HOST_COPIES = 0                # device-to-host copies made by this module so far: each is one host synchronisation
-_lib = None
-
-
-def lib():
-    """Loads libtd_explorer.so; raises if it has not been built.  There is no CPU fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TdError(f"{LIB_PATH} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(l, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise TdError(f"td_explorer error {rc}: {lib().td_explorer_last_error().decode()}")
+_LIB = Library("libtd_explorer.so", _SIGS, "td_explorer_last_error", "td_explorer")
+LIB_PATH, lib, check = _LIB.path, _LIB.lib, _LIB.check
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ colour tables
 _RDBU = ((103, 0, 31), (178, 24, 43), (214, 96, 77), (244, 165, 130), (253, 219, 199), (247, 247, 247), (209, 229, 240), (146, 197, 222),
          (67, 147, 195), (33, 102, 172), (5, 48, 97))   # ColorBrewer RdBu, 11 classes
-
-
-def _segment_lut(pos, colors, n=256):
-    """(n, 3) float32 rows of a piecewise-linear colormap through `colors` at `pos`, as matplotlib's lookup-table builder forms them
-    (float64, clipped to [0, 1]): the construction of relief.terrain_lut."""
-    x = np.asarray(pos, dtype=np.float64) * (n - 1)
-    xind = (n - 1) * np.linspace(0, 1, n)
-    ind = np.searchsorted(x, xind)[1:-1]
-    distance = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
-    lut = np.empty((n, 3), dtype=np.float64)
-    for c in range(3):
-        y = np.array([rgb[c] for rgb in colors], dtype=np.float64)
-        lut[:, c] = np.concatenate([[y[0]], distance * (y[ind] - y[ind - 1]) + y[ind - 1], [y[-1]]])
-    return np.clip(lut, 0.0, 1.0).astype(np.float32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -103,7 +67,7 @@ def colormap_lut(name):
     elif name == "RdBu_r":
         # RdBu is from_list over linspace(0, 1, 11); the reversed map runs through (1.0 - x, colour) of the reversed list
         pos = [1.0 - x for x in reversed(np.linspace(0, 1, len(_RDBU)))]
-        out = _segment_lut(pos, [tuple(v / 255 for v in rgb) for rgb in reversed(_RDBU)])
+        out = _relief._segment_lut(pos, [tuple(v / 255 for v in rgb) for rgb in reversed(_RDBU)])
     else:
         raise ValueError(f"unknown colormap {name!r}: 'viridis', 'terrain' or 'RdBu_r' (or pass a (256, 3) table)")
     out.flags.writeable = False
@@ -118,16 +82,8 @@ def _device_lut(device_index, name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- plumbing
-def _shape(x):
-    return tuple(int(d) for d in x.shape)
-
-
 def _hw(H, W):
-    if H < 1 or W < 1:
-        raise ValueError(f"empty field: {H} x {W} pixels")
-    if H > MAX_SIDE or W > MAX_SIDE or H * W > MAX_PIXELS:
-        raise ValueError(f"field {H} x {W} beyond the library's limit (H, W <= 2^16, H * W <= 2^26 pixels)")
-    return H, W
+    return hw(H, W, "field")
 
 
 def _plane(x, what):
@@ -136,47 +92,8 @@ def _plane(x, what):
     return _hw(*_shape(x))
 
 
-def _engine_for(x, engine):
-    if engine is None:
-        engine = get_engine(x.device if (torch.is_tensor(x) and x.is_cuda) else None)
-    return engine, torch.device("cuda", engine.device_id)
-
-
-def _f32(x, dev):
-    """Contiguous fp32 device tensor of a numpy array or tensor (no copy when it already is one)."""
-    if not torch.is_tensor(x):
-        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
-    return x.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-
 def _dp(t):
     return None if t is None else C.c_void_p(t.data_ptr())
-
-
-class _Ordered:
-    """Orders the engine's stream with torch's current stream WITHOUT a host synchronisation: on entry the engine's stream waits for what
-    torch has enqueued (the inputs), on exit torch's stream waits for the engine's (the outputs).  Nothing to do when the engine already
-    launches on torch's current stream (Engine.on_stream)."""
-
-    def __init__(self, engine, dev):
-        cur = torch.cuda.current_stream(dev)
-        self.cur, self.ext = cur, None
-        if _SHARED_STREAM.get(engine.device_id) != cur.cuda_stream:
-            self.ext = torch.cuda.ExternalStream(int(engine.stream), device=dev)
-
-    def __enter__(self):
-        if self.ext is not None:
-            self.ext.wait_stream(self.cur)
-        return self
-
-    def __exit__(self, *exc):
-        if self.ext is not None:
-            self.cur.wait_stream(self.ext)
-        return False
-
-
-def _sync_flag(engine, enqueue_only):
-    return 0 if (enqueue_only or engine._async) else 1
 
 
 def _host(*tensors):
@@ -213,9 +130,8 @@ def _channels(engine, dev, sums, n_signed_sq, eps, enqueue_only):
     s = _f32(sums, dev)
     out = torch.empty((Cn, H, W), dtype=torch.float32, device=dev)
     minmax = torch.empty((Cn, 2), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _Ordered(engine, dev):
-        check(lib().td_explorer_channels(C.c_void_p(engine.stream), _dp(s), Cn, H, W, int(n_signed_sq), float(eps), _dp(out), _dp(minmax),
-                                         _sync_flag(engine, enqueue_only)))
+    call(_LIB, "td_explorer_channels", engine, dev, _dp(s), Cn, H, W, int(n_signed_sq), float(eps), _dp(out), _dp(minmax),
+         enqueue_only=enqueue_only, ordered=True)
     return out, minmax
 
 
@@ -274,10 +190,8 @@ def _colorize(engine, dev, field, cmap, log1p, vmin, vmax, filters, enqueue_only
     n, planes, lo, hi, use_lo, use_hi, keep = _filter_args(filters, dev)
     out = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
     rng = torch.empty(2, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _Ordered(engine, dev):
-        check(lib().td_explorer_colorize(C.c_void_p(engine.stream), _dp(f), H, W, int(bool(log1p)), int(has_range), float(vmin) if has_range else 0.0,
-                                         float(vmax) if has_range else 0.0, _dp(lut), n, planes, lo, hi, use_lo, use_hi, _dp(out), _dp(rng),
-                                         _sync_flag(engine, enqueue_only)))
+    call(_LIB, "td_explorer_colorize", engine, dev, _dp(f), H, W, int(bool(log1p)), int(has_range), float(vmin) if has_range else 0.0,
+         float(vmax) if has_range else 0.0, _dp(lut), n, planes, lo, hi, use_lo, use_hi, _dp(out), _dp(rng), enqueue_only=enqueue_only, ordered=True)
     del keep
     return out, rng
 
@@ -311,8 +225,7 @@ def _quantize(engine, dev, rgb, enqueue_only):
     H, W = _check_rgb(rgb)
     r = _f32(rgb, dev)
     out = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev), _Ordered(engine, dev):
-        check(lib().td_explorer_quantize(C.c_void_p(engine.stream), _dp(r), H, W, _dp(out), _sync_flag(engine, enqueue_only)))
+    call(_LIB, "td_explorer_quantize", engine, dev, _dp(r), H, W, _dp(out), enqueue_only=enqueue_only, ordered=True)
     return out
 
 
@@ -337,8 +250,7 @@ def _raw(engine, dev, elev, temp, enqueue_only):
     e = _f32(elev, dev)
     t = None if temp is None else _f32(temp, dev)
     out = torch.empty((6 if t is not None else 2) * H * W, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev), _Ordered(engine, dev):
-        check(lib().td_explorer_raw(C.c_void_p(engine.stream), _dp(e), _dp(t), H, W, _dp(out), _sync_flag(engine, enqueue_only)))
+    call(_LIB, "td_explorer_raw", engine, dev, _dp(e), _dp(t), H, W, _dp(out), enqueue_only=enqueue_only, ordered=True)
     return out
 
 
@@ -369,9 +281,8 @@ def _land(engine, dev, elev_m, half, min_land_frac, enqueue_only):
     cap = 0 if half == 0 else (H - 2 * half) * (W - 2 * half)
     idx = torch.empty(cap, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev), _Ordered(engine, dev):
-        check(lib().td_explorer_land_tiles(C.c_void_p(engine.stream), _dp(e), H, W, half, float(min_land_frac), _dp(idx) if cap else None, _dp(count),
-                                           _sync_flag(engine, enqueue_only)))
+    call(_LIB, "td_explorer_land_tiles", engine, dev, _dp(e), H, W, half, float(min_land_frac), _dp(idx) if cap else None, _dp(count),
+         enqueue_only=enqueue_only, ordered=True)
     return idx, count
 
 
@@ -456,10 +367,8 @@ def _relief_enqueue(engine, dev, e, resolution):
     fill = _relief._nanmedian(e) if has_fill else None
     lut, wl, rl, ws, rs = _relief._device_tables(engine.device_id, 6.0, 1.2)
     out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _Ordered(engine, dev):
-        _relief.check(_relief.lib().td_relief_map(C.c_void_p(engine.stream), _dp(e), H, W, _dp(lut), _dp(wl), rl, _dp(ws), rs,
-                                                  float(_relief.DEFAULT_AZIMUTHS[0]), float(resolution), 1.0, 0, 0.0, 0.0, int(has_fill),
-                                                  float(fill) if has_fill else 0.0, _dp(out), 0))
+    call(_relief._LIB, "td_relief_map", engine, dev, _dp(e), H, W, _dp(lut), _dp(wl), rl, _dp(ws), rs, float(_relief.DEFAULT_AZIMUTHS[0]),
+         float(resolution), 1.0, 0, 0.0, 0.0, int(has_fill), float(fill) if has_fill else 0.0, _dp(out), enqueue_only=True, ordered=True)
     return out
 
 

@@ -1,45 +1,18 @@
 // libtd_explorer.so: the C-ABI of include/td_explorer.h over the kernels of explorer_kernels.hip.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <string>
 
+#include "../side_csrc/td_side_host.h"
 #include "../../include/td_explorer.h"
 #include "explorer_kernels.hip"
 
 using namespace td;
 
 namespace {
-enum { OK = 0, ERR_ARG = -1, ERR_HIP = -2 };
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define EX_HIP_TRY(expr)                                                                                         \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return fail(ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-    } while (0)
-
-bool is_device_ptr(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 bool size_ok(int H, int W) {
     return H >= 1 && W >= 1 && H <= TD_EXPLORER_MAX_SIDE && W <= TD_EXPLORER_MAX_SIDE && (long long)H * W <= TD_EXPLORER_MAX_PIXELS;
 }
 const char* const SIZE_MSG = ": needs 1 <= H, W <= 2^16 and H * W <= 2^26";
-unsigned blocks(long long n) { return (unsigned)((n + EX_THREADS - 1) / EX_THREADS); }
-unsigned reduce_blocks(long long n) { return blocks(n) < EX_REDUCE_BLOCKS ? blocks(n) : EX_REDUCE_BLOCKS; }
-
-// frees the scratch in stream order, reports the first error, synchronises on request
-int finish(hipStream_t st, void* scratch, hipError_t err, int synchronize) {
-    const hipError_t ferr = scratch ? hipFreeAsync(scratch, st) : hipSuccess;
-    EX_HIP_TRY(err);
-    EX_HIP_TRY(ferr);
-    if (synchronize) EX_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
-}
+unsigned reduce_blocks(long long n) { return blocks(n, EX_THREADS) < EX_REDUCE_BLOCKS ? blocks(n, EX_THREADS) : EX_REDUCE_BLOCKS; }
 }  // namespace
 
 extern "C" {
@@ -59,7 +32,7 @@ int td_explorer_channels(void* hip_stream, const float* sums, int C, int H, int 
     void* scratch = nullptr;
     hipError_t err = hipSuccess;
     if (minmax) {
-        EX_HIP_TRY(hipMallocAsync(&scratch, 2 * TD_EXPLORER_MAX_CHANNELS * sizeof(unsigned), st));
+        TD_HIP_TRY(hipMallocAsync(&scratch, 2 * TD_EXPLORER_MAX_CHANNELS * sizeof(unsigned), st));
         err = hipMemsetAsync(scratch, 0, 2 * TD_EXPLORER_MAX_CHANNELS * sizeof(unsigned), st);
     }
     if (err == hipSuccess) {
@@ -93,14 +66,14 @@ int td_explorer_colorize(void* hip_stream, const float* field, int H, int W, int
     void* scratch = nullptr;
     hipError_t err = hipSuccess;
     if (!has_range) {
-        EX_HIP_TRY(hipMallocAsync(&scratch, 2 * sizeof(unsigned), st));
+        TD_HIP_TRY(hipMallocAsync(&scratch, 2 * sizeof(unsigned), st));
         err = hipMemsetAsync(scratch, 0, 2 * sizeof(unsigned), st);
     }
     a.field = field; a.n = n; a.log1p_on = log1p ? 1 : 0; a.has_range = has_range ? 1 : 0; a.vmin = vmin; a.vmax = vmax;
     a.words = (const unsigned*)scratch; a.lut = lut; a.n_filters = n_filters; a.out = (uchar4*)out; a.range_out = range_out;
     if (err == hipSuccess) {
         if (!has_range) hipLaunchKernelGGL(ex_range_kernel, dim3(reduce_blocks(n)), dim3(EX_THREADS), 0, st, field, n, a.log1p_on, (unsigned*)scratch);
-        hipLaunchKernelGGL(ex_color_kernel, dim3(blocks(n)), dim3(EX_THREADS), 0, st, a);
+        hipLaunchKernelGGL(ex_color_kernel, dim3(blocks(n, EX_THREADS)), dim3(EX_THREADS), 0, st, a);
         err = hipGetLastError();
     }
     return finish(st, scratch, err, synchronize);
@@ -111,7 +84,7 @@ int td_explorer_quantize(void* hip_stream, const float* rgb, int H, int W, uint8
     if (!is_device_ptr(rgb) || !is_device_ptr(out)) return fail(ERR_ARG, "td_explorer_quantize: device buffers only");
     hipStream_t st = (hipStream_t)hip_stream;
     const long long n = (long long)H * W;
-    hipLaunchKernelGGL(ex_quantize_kernel, dim3(blocks(n)), dim3(EX_THREADS), 0, st, rgb, n, (uchar4*)out);
+    hipLaunchKernelGGL(ex_quantize_kernel, dim3(blocks(n, EX_THREADS)), dim3(EX_THREADS), 0, st, rgb, n, (uchar4*)out);
     return finish(st, nullptr, hipGetLastError(), synchronize);
 }
 
@@ -121,7 +94,7 @@ int td_explorer_raw(void* hip_stream, const float* elev, const float* temp, int 
     if ((uintptr_t)out & 1u) return fail(ERR_ARG, "td_explorer_raw: out needs 2-byte alignment");
     hipStream_t st = (hipStream_t)hip_stream;
     const long long n = (long long)H * W;
-    hipLaunchKernelGGL(ex_raw_kernel, dim3(blocks(n)), dim3(EX_THREADS), 0, st, elev, temp, n, (uint16_t*)out);
+    hipLaunchKernelGGL(ex_raw_kernel, dim3(blocks(n, EX_THREADS)), dim3(EX_THREADS), 0, st, elev, temp, n, (uint16_t*)out);
     return finish(st, nullptr, hipGetLastError(), synchronize);
 }
 
@@ -136,15 +109,15 @@ int td_explorer_land_tiles(void* hip_stream, const float* elev_m, int H, int W, 
     if (capacity > 0 && !is_device_ptr(out_idx)) return fail(ERR_ARG, "td_explorer_land_tiles: device buffers only");
     hipStream_t st = (hipStream_t)hip_stream;
     if (capacity == 0) {
-        EX_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int32_t), st));
+        TD_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int32_t), st));
         return finish(st, nullptr, hipSuccess, synchronize);
     }
     const long long n = (long long)H * W;
-    const unsigned nb = blocks(n);
+    const unsigned nb = blocks(n, EX_THREADS);
     // scratch: the row counts (uint16 per pixel), the flags (uint8 per pixel), the per-block counts (uint32)
     const size_t rows_bytes = ((size_t)n * 2 + 255) & ~(size_t)255, flags_bytes = ((size_t)n + 255) & ~(size_t)255;
     void* scratch = nullptr;
-    EX_HIP_TRY(hipMallocAsync(&scratch, rows_bytes + flags_bytes + (size_t)nb * sizeof(unsigned), st));
+    TD_HIP_TRY(hipMallocAsync(&scratch, rows_bytes + flags_bytes + (size_t)nb * sizeof(unsigned), st));
     uint16_t* rows = (uint16_t*)scratch;
     uint8_t* flags = (uint8_t*)scratch + rows_bytes;
     unsigned* counts = (unsigned*)((uint8_t*)scratch + rows_bytes + flags_bytes);

@@ -1,35 +1,17 @@
 // libtd_hydro.so: the C-ABI of include/td_hydro.h over the kernels of hydro_kernels.hip.
-#include <hip/hip_runtime.h>
-#include <string>
-
+#include "../side_csrc/td_side_host.h"
 #include "../../include/td_hydro.h"
 #include "hydro_kernels.hip"
 
 using namespace td;
 
 namespace {
-enum { OK = 0, ERR_ARG = -1, ERR_HIP = -2, ERR_CONVERGE = -3 };
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HYDRO_HIP_TRY(expr)                                                                                      \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return fail(ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-    } while (0)
-
-bool is_device_ptr(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
+enum { ERR_CONVERGE = -3 };
 constexpr long long MAX_SIDE = 1LL << 20, MAX_CELLS_D8 = (1LL << 31) - 1, MAX_CELLS_ACC = 1LL << 24;
 // d8 and fill: 1 <= H, W <= 2^20, H W < 2^31; accumulation and indicator: H W <= 2^24 (upstream counts stay exact in fp32)
 bool size_ok(int H, int W, long long max_cells) {
     return H >= 1 && W >= 1 && H <= MAX_SIDE && W <= MAX_SIDE && (long long)H * W <= max_cells;
 }
-unsigned blocks(long long n) { return (unsigned)((n + HYDRO_THREADS - 1) / HYDRO_THREADS); }
 constexpr int FILL_BATCH = 8;   // passes enqueued between two reads of the convergence flags
 }  // namespace
 
@@ -42,10 +24,8 @@ int td_hydro_d8(void* hip_stream, const float* z, int H, int W, double tol, int3
     if (!is_device_ptr(z) || !is_device_ptr(receiver) || !is_device_ptr(kmax) || !is_device_ptr(is_sink))
         return fail(ERR_ARG, "td_hydro_d8: device buffers only");
     hipStream_t st = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(hydro_d8_kernel, dim3(blocks((long long)H * W)), dim3(HYDRO_THREADS), 0, st, z, H, W, (float)tol, receiver, kmax, is_sink);
-    HYDRO_HIP_TRY(hipGetLastError());
-    if (synchronize) HYDRO_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
+    hipLaunchKernelGGL(hydro_d8_kernel, dim3(blocks((long long)H * W, HYDRO_THREADS)), dim3(HYDRO_THREADS), 0, st, z, H, W, (float)tol, receiver, kmax, is_sink);
+    return finish(st, nullptr, hipGetLastError(), synchronize);
 }
 
 int td_hydro_accumulate(void* hip_stream, const float* z, int H, int W, const int32_t* receiver, const uint8_t* is_sink, float* acc,
@@ -57,22 +37,18 @@ int td_hydro_accumulate(void* hip_stream, const float* z, int H, int W, const in
     const int N = H * W;
     // scratch: the per-cell (count, pending) words and the counted-edge successors, from the stream-ordered pool
     void* scratch = nullptr;
-    HYDRO_HIP_TRY(hipMallocAsync(&scratch, (size_t)N * 12, st));
+    TD_HIP_TRY(hipMallocAsync(&scratch, (size_t)N * 12, st));
     unsigned long long* word = (unsigned long long*)scratch;
     int32_t* next = (int32_t*)(word + N);
     hipError_t err = hipMemsetAsync(bad_edges, 0, sizeof(uint32_t), st);
     if (err == hipSuccess) {
-        hipLaunchKernelGGL(hydro_acc_init_kernel, dim3(blocks(N)), dim3(HYDRO_THREADS), 0, st, z, N, word);
-        hipLaunchKernelGGL(hydro_acc_edges_kernel, dim3(blocks(N)), dim3(HYDRO_THREADS), 0, st, z, N, receiver, is_sink, next, word, (unsigned*)bad_edges);
-        hipLaunchKernelGGL(hydro_acc_walk_kernel, dim3(blocks(N)), dim3(HYDRO_THREADS), 0, st, N, (const int32_t*)next, word);
-        hipLaunchKernelGGL(hydro_acc_out_kernel, dim3(blocks(N)), dim3(HYDRO_THREADS), 0, st, N, (const unsigned long long*)word, acc);
+        hipLaunchKernelGGL(hydro_acc_init_kernel, dim3(blocks(N, HYDRO_THREADS)), dim3(HYDRO_THREADS), 0, st, z, N, word);
+        hipLaunchKernelGGL(hydro_acc_edges_kernel, dim3(blocks(N, HYDRO_THREADS)), dim3(HYDRO_THREADS), 0, st, z, N, receiver, is_sink, next, word, (unsigned*)bad_edges);
+        hipLaunchKernelGGL(hydro_acc_walk_kernel, dim3(blocks(N, HYDRO_THREADS)), dim3(HYDRO_THREADS), 0, st, N, (const int32_t*)next, word);
+        hipLaunchKernelGGL(hydro_acc_out_kernel, dim3(blocks(N, HYDRO_THREADS)), dim3(HYDRO_THREADS), 0, st, N, (const unsigned long long*)word, acc);
         err = hipGetLastError();
     }
-    const hipError_t ferr = hipFreeAsync(scratch, st);
-    HYDRO_HIP_TRY(err);
-    HYDRO_HIP_TRY(ferr);
-    if (synchronize) HYDRO_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
+    return finish(st, scratch, err, synchronize);
 }
 
 int td_hydro_indicator(void* hip_stream, const float* acc, int H, int W, int k, float* out, int synchronize) {
@@ -81,10 +57,8 @@ int td_hydro_indicator(void* hip_stream, const float* acc, int H, int W, int k, 
     if (!is_device_ptr(acc) || !is_device_ptr(out)) return fail(ERR_ARG, "td_hydro_indicator: device buffers only");
     hipStream_t st = (hipStream_t)hip_stream;
     const int Ho = H / k, Wo = W / k;
-    hipLaunchKernelGGL(hydro_indicator_kernel, dim3(blocks((long long)Ho * Wo)), dim3(HYDRO_THREADS), 0, st, acc, W, k, Ho, Wo, out);
-    HYDRO_HIP_TRY(hipGetLastError());
-    if (synchronize) HYDRO_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
+    hipLaunchKernelGGL(hydro_indicator_kernel, dim3(blocks((long long)Ho * Wo, HYDRO_THREADS)), dim3(HYDRO_THREADS), 0, st, acc, W, k, Ho, Wo, out);
+    return finish(st, nullptr, hipGetLastError(), synchronize);
 }
 
 int td_hydro_fill(void* hip_stream, const float* h, int H, int W, double epsilon, int connectivity, int has_nodata, double nodata, float* out,
@@ -101,14 +75,14 @@ int td_hydro_fill(void* hip_stream, const float* h, int H, int W, double epsilon
     const size_t ntiles = (size_t)ntx * nty;
     // scratch: hw (N floats), two tile-flag planes, FILL_BATCH + 1 pass flags
     void* scratch = nullptr;
-    HYDRO_HIP_TRY(hipMallocAsync(&scratch, (size_t)N * 4 + 2 * ntiles * 4 + (FILL_BATCH + 1) * 4, st));
+    TD_HIP_TRY(hipMallocAsync(&scratch, (size_t)N * 4 + 2 * ntiles * 4 + (FILL_BATCH + 1) * 4, st));
     float* hw = (float*)scratch;
     unsigned* tiles = (unsigned*)(hw + N);
     unsigned* flags = tiles + 2 * ntiles;
     unsigned host_flags[FILL_BATCH + 1];
     const long long max_passes = N + 2;   // every pass that changes something completes at least one more step of some cell's flood path
     long long done = 0, converged_at = -1;
-    hipLaunchKernelGGL(hydro_fill_init_kernel, dim3(blocks(N)), dim3(HYDRO_THREADS), 0, st, h, H, W, conn8, has_nodata ? 1 : 0, nd, out, hw);
+    hipLaunchKernelGGL(hydro_fill_init_kernel, dim3(blocks(N, HYDRO_THREADS)), dim3(HYDRO_THREADS), 0, st, h, H, W, conn8, has_nodata ? 1 : 0, nd, out, hw);
     hipError_t err = hipGetLastError();
     while (err == hipSuccess && converged_at < 0 && done < max_passes) {
         err = hipMemsetAsync(flags, 0, (FILL_BATCH + 1) * 4, st);
@@ -128,13 +102,10 @@ int td_hydro_fill(void* hip_stream, const float* h, int H, int W, double epsilon
         }
     }
     if (err == hipSuccess && converged_at >= 0) {
-        hipLaunchKernelGGL(hydro_fill_out_kernel, dim3(blocks(N)), dim3(HYDRO_THREADS), 0, st, h, (size_t)N, has_nodata ? 1 : 0, nd, out);
+        hipLaunchKernelGGL(hydro_fill_out_kernel, dim3(blocks(N, HYDRO_THREADS)), dim3(HYDRO_THREADS), 0, st, h, (size_t)N, has_nodata ? 1 : 0, nd, out);
         err = hipGetLastError();
     }
-    const hipError_t ferr = hipFreeAsync(scratch, st);
-    HYDRO_HIP_TRY(err);
-    HYDRO_HIP_TRY(ferr);
-    HYDRO_HIP_TRY(hipStreamSynchronize(st));
+    if (const int rc = finish(st, scratch, err, 1)) return rc;   // always synchronises: converged_at and *passes are read on the host
     if (converged_at < 0) return fail(ERR_CONVERGE, "td_hydro_fill: no convergence within H * W + 2 passes");
     if (passes) *passes = (int)(converged_at > 0x7fffffff ? 0x7fffffff : converged_at);
     return OK;

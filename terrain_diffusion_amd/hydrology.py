@@ -10,15 +10,14 @@ The contract is fp32 elevation (what WorldPipeline.get returns).  Other dtypes a
 in float64, its result can differ.  There is no CPU fallback.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
-from ._lib import TdError
-from .engine import get_engine, ptr
+from ._lib import Library
+from ._plumbing import call, engine_for as _engine_for, f32 as _f32
+from .engine import ptr
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtd_hydro.so")
 _P = C.c_void_p
 _SIGS = {
     "td_hydro_last_error": (C.c_char_p, []),
@@ -30,27 +29,8 @@ _SIGS = {
 EXPORTS = tuple(_SIGS)
 MAX_SIDE = 1 << 20          # d8 and fill: H, W <= 2^20, H * W < 2^31
 MAX_CELLS_ACC = 1 << 24     # accumulation and indicator: upstream counts stay exact in fp32
-_lib = None
-
-
-def lib():
-    """Loads libtd_hydro.so; raises if it has not been built.  There is no CPU fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TdError(f"{LIB_PATH} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(l, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise TdError(f"td_hydro error {rc}: {lib().td_hydro_last_error().decode()}")
+_LIB = Library("libtd_hydro.so", _SIGS, "td_hydro_last_error", "td_hydro")
+LIB_PATH, lib, check = _LIB.path, _LIB.lib, _LIB.check
 
 
 def _check_shape(shape, max_cells):
@@ -60,23 +40,6 @@ def _check_shape(shape, max_cells):
     if H < 1 or W < 1 or H > MAX_SIDE or W > MAX_SIDE or H * W > max_cells:
         raise ValueError(f"elevation (H, W) = {(H, W)} outside 1 <= H, W <= 2^20, H * W <= {max_cells}")
     return H, W
-
-
-def _engine_for(x, engine):
-    if engine is None:
-        engine = get_engine(x.device if (torch.is_tensor(x) and x.is_cuda) else None)
-    return engine, torch.device("cuda", engine.device_id)
-
-
-def _f32(x, dev):
-    """Contiguous fp32 device tensor of a numpy array or tensor (no copy when it already is one)."""
-    if not torch.is_tensor(x):
-        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
-    return x.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-
-def _sync_flag(engine):
-    return 0 if engine._async else 1
 
 
 @torch.no_grad()
@@ -89,8 +52,7 @@ def flow_directions(z, tol=1e-3, *, engine=None):
     receiver = torch.empty((H, W), dtype=torch.int32, device=dev)
     kmax = torch.empty((H, W), dtype=torch.uint8, device=dev)
     sink = torch.empty((H, W), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().td_hydro_d8(C.c_void_p(engine.stream), ptr(e), H, W, float(tol), ptr(receiver), ptr(kmax), ptr(sink), _sync_flag(engine)))
+    call(_LIB, "td_hydro_d8", engine, dev, ptr(e), H, W, float(tol), ptr(receiver), ptr(kmax), ptr(sink))
     return receiver, kmax, sink.view(torch.bool)
 
 
@@ -108,9 +70,7 @@ def flow_accumulation_map(z, receiver, is_sink, *, engine=None):
         raise ValueError(f"receiver {tuple(r.shape)} and is_sink {tuple(s.shape)} must have the elevation's shape {(H, W)}")
     acc = torch.empty((H, W), dtype=torch.float32, device=dev)
     bad = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().td_hydro_accumulate(C.c_void_p(engine.stream), ptr(e), H, W, ptr(r), ptr(s.view(torch.uint8)), ptr(acc), ptr(bad),
-                                        _sync_flag(engine)))
+    call(_LIB, "td_hydro_accumulate", engine, dev, ptr(e), H, W, ptr(r), ptr(s.view(torch.uint8)), ptr(acc), ptr(bad))
     n_bad = int(bad.item())
     if n_bad:
         raise ValueError(f"flow_accumulation: {n_bad} counted edge(s) are not strictly downhill (or point outside the image); the reference's "
@@ -126,8 +86,7 @@ def _indicator_of(acc, max_pool_kernel, engine, dev):
     out = torch.empty((Ho, Wo), dtype=torch.float32, device=dev)
     if Ho == 0 or Wo == 0:
         return out
-    with torch.cuda.device(dev):
-        check(lib().td_hydro_indicator(C.c_void_p(engine.stream), ptr(acc), H, W, k, ptr(out), _sync_flag(engine)))
+    call(_LIB, "td_hydro_indicator", engine, dev, ptr(acc), H, W, k, ptr(out))
     return out
 
 
@@ -161,7 +120,7 @@ def fill_depressions(height, epsilon=1e-3, connectivity=8, nodata=None, *, retur
     h = _f32(height, dev)
     out = torch.empty((H, W), dtype=torch.float32, device=dev)
     passes = C.c_int(0)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev):   # no synchronize argument: td_hydro_fill always synchronises
         check(lib().td_hydro_fill(C.c_void_p(engine.stream), ptr(h), H, W, eps, int(connectivity), int(nodata is not None),
                                   float(nodata) if nodata is not None else 0.0, ptr(out), C.byref(passes)))
     return (out, passes.value) if return_passes else out

@@ -1,33 +1,14 @@
 // libtd_mc.so: the C-ABI of include/td_mc.h over the kernels of mc_kernels.hip.
-#include <hip/hip_runtime.h>
-#include <string>
-
+#include "../side_csrc/td_side_host.h"
 #include "../../include/td_mc.h"
 #include "mc_kernels.hip"
 
 using namespace td;
 
 namespace {
-enum { OK = 0, ERR_ARG = -1, ERR_HIP = -2 };
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define MC_HIP_TRY(expr)                                                                                         \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return fail(ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-    } while (0)
-
-bool is_device_ptr(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 bool size_ok(int H, int W) {
     return H >= 1 && W >= 1 && H <= TD_MC_MAX_SIDE && W <= TD_MC_MAX_SIDE && (long long)H * W <= TD_MC_MAX_PIXELS;
 }
-unsigned blocks(long long n) { return (unsigned)((n + MC_THREADS - 1) / MC_THREADS); }
 }  // namespace
 
 extern "C" {
@@ -43,11 +24,9 @@ int td_mc_upsample(void* hip_stream, const float* src, int C, int Hn, int Wn, in
         return fail(ERR_ARG, "td_mc_upsample: the box must lie inside the (Hn * scale, Wn * scale) upsampled image");
     if (!is_device_ptr(src) || !is_device_ptr(out)) return fail(ERR_ARG, "td_mc_upsample: device buffers only");
     hipStream_t st = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(mc_upsample_kernel, dim3(blocks((long long)H * W), C), dim3(MC_THREADS), 0, st, src, C, Hn, Wn, scale, (float)(1.0 / scale), r0, c0, H, W,
+    hipLaunchKernelGGL(mc_upsample_kernel, dim3(blocks((long long)H * W, MC_THREADS), C), dim3(MC_THREADS), 0, st, src, C, Hn, Wn, scale, (float)(1.0 / scale), r0, c0, H, W,
                        out);
-    MC_HIP_TRY(hipGetLastError());
-    if (synchronize) MC_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
+    return finish(st, nullptr, hipGetLastError(), synchronize);
 }
 
 int td_mc_finish(void* hip_stream, const float* elev, long long elev_ld, const float* elev_padded, const float* climate, int n_climate, int H,
@@ -75,19 +54,15 @@ int td_mc_finish(void* hip_stream, const float* elev, long long elev_ld, const f
     a.elev_out = elev_out; a.biome_out = biome_out;
     hipStream_t st = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(mc_finish_kernel, dim3((W + MC_TILE - 1) / MC_TILE, (H + MC_TILE - 1) / MC_TILE), dim3(MC_TILE * MC_TILE), 0, st, a);
-    MC_HIP_TRY(hipGetLastError());
-    if (synchronize) MC_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
+    return finish(st, nullptr, hipGetLastError(), synchronize);
 }
 
 int td_mc_noise(void* hip_stream, int H, int W, long long i0, long long j0, float* out, int synchronize) {
     if (!size_ok(H, W)) return fail(ERR_ARG, "td_mc_noise: needs 1 <= H, W <= 2^16 and H * W <= 2^26");
     if (!is_device_ptr(out)) return fail(ERR_ARG, "td_mc_noise: device buffers only");
     hipStream_t st = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(mc_noise_kernel, dim3(blocks((long long)H * W)), dim3(MC_THREADS), 0, st, H, W, i0, j0, out);
-    MC_HIP_TRY(hipGetLastError());
-    if (synchronize) MC_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
+    hipLaunchKernelGGL(mc_noise_kernel, dim3(blocks((long long)H * W, MC_THREADS)), dim3(MC_THREADS), 0, st, H, W, i0, j0, out);
+    return finish(st, nullptr, hipGetLastError(), synchronize);
 }
 
 int td_mc_payload(void* hip_stream, const float* elev, const int16_t* biome, int H, int W, int16_t* out, int synchronize) {
@@ -95,10 +70,8 @@ int td_mc_payload(void* hip_stream, const float* elev, const int16_t* biome, int
     if (!is_device_ptr(elev) || !is_device_ptr(out) || (biome && !is_device_ptr(biome))) return fail(ERR_ARG, "td_mc_payload: device buffers only");
     hipStream_t st = (hipStream_t)hip_stream;
     const long long n = (long long)H * W;
-    hipLaunchKernelGGL(mc_payload_kernel, dim3(blocks(n)), dim3(MC_THREADS), 0, st, elev, biome, n, out);
-    MC_HIP_TRY(hipGetLastError());
-    if (synchronize) MC_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
+    hipLaunchKernelGGL(mc_payload_kernel, dim3(blocks(n, MC_THREADS)), dim3(MC_THREADS), 0, st, elev, biome, n, out);
+    return finish(st, nullptr, hipGetLastError(), synchronize);
 }
 
 }  // extern "C"

@@ -15,15 +15,14 @@ Index arithmetic is Python's (floor division, also for negative coordinates); no
 Inputs of other dtypes are cast to fp32.  There is no CPU fallback.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
-from ._lib import TdError
+from ._lib import Library
+from ._plumbing import MAX_PIXELS, MAX_SIDE, call, engine_for as _engine_for, f32 as _f32, hw, shape as _shape  # noqa: F401
 from .engine import get_engine, ptr
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtd_mc.so")
 _P = C.c_void_p
 _LL = C.c_longlong
 _SIGS = {
@@ -35,31 +34,10 @@ _SIGS = {
     "td_mc_payload": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int]),
 }
 EXPORTS = tuple(_SIGS)
-MAX_SIDE = 1 << 16          # per call: 1 <= H, W <= 2^16 ...
-MAX_PIXELS = 1 << 26        # ... and H * W <= 2^26 output pixels (include/td_mc.h)
 NOISE_NAMES = ("_TEMP_NOISE", "_TEMP_NOISE_FINE", "_PRECIP_NOISE", "_SNOW_NOISE", "_SNOW_NOISE_FINE", "_ELEV_NOISE_COARSE", "_ELEV_NOISE_FINE")
 _CLIMATE_NOISE, _DETAIL_NOISE = (0, 1, 2, 3, 4), (5, 6)
-_lib = None
-
-
-def lib():
-    """Loads libtd_mc.so; raises if it has not been built.  There is no CPU fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TdError(f"{LIB_PATH} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(l, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise TdError(f"td_mc error {rc}: {lib().td_mc_last_error().decode()}")
+_LIB = Library("libtd_mc.so", _SIGS, "td_mc_last_error", "td_mc")
+LIB_PATH, lib, check = _LIB.path, _LIB.lib, _LIB.check
 
 
 # ----------------------------------------------------------------------------------------------------------------------------- validation
@@ -70,11 +48,7 @@ def _scale(scale):
 
 
 def _hw(H, W):
-    if H < 1 or W < 1:
-        raise ValueError(f"empty box: {H} x {W} pixels")
-    if H > MAX_SIDE or W > MAX_SIDE or H * W > MAX_PIXELS:
-        raise ValueError(f"box {H} x {W} beyond the library's limit (H, W <= 2^16, H * W <= 2^26 pixels)")
-    return H, W
+    return hw(H, W, "box")
 
 
 def _box(i1, j1, i2, j2):
@@ -87,33 +61,12 @@ def _native_box(i1, j1, i2, j2, s, pad):
     return i1 // s - pad, j1 // s - pad, -(-i2 // s) + pad, -(-j2 // s) + pad
 
 
-def _shape(x):
-    return tuple(int(d) for d in x.shape)
-
-
 def _check_climate(climate, H, W):
     if climate is not None and (len(_shape(climate)) != 3 or _shape(climate)[1:] != (H, W)):
         raise ValueError(f"climate {_shape(climate)} must be (C, {H}, {W})")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- plumbing
-def _engine_for(x, engine):
-    if engine is None:
-        engine = get_engine(x.device if (torch.is_tensor(x) and x.is_cuda) else None)
-    return engine, torch.device("cuda", engine.device_id)
-
-
-def _f32(x, dev):
-    """Contiguous fp32 device tensor of a numpy array or tensor (no copy when it already is one)."""
-    if not torch.is_tensor(x):
-        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
-    return x.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-
-def _sync_flag(engine):
-    return 0 if engine._async else 1
-
-
 def _fetch(world, box, with_climate, dev):
     """world.get of a native box -> (elev (h, w), climate (C, h, w) or None) as fp32 device tensors, shapes checked."""
     a, b, c, d = box
@@ -129,8 +82,7 @@ def _upsample(src, s, r0, c0, H, W, engine, dev):
     """Rows [r0, r0 + H) x columns [c0, c0 + W) of the bilinear upsample by s of src (C, Hn, Wn) -> (C, H, W)."""
     Cn, Hn, Wn = _shape(src)
     out = torch.empty((Cn, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().td_mc_upsample(C.c_void_p(engine.stream), ptr(src), Cn, Hn, Wn, s, r0, c0, H, W, ptr(out), _sync_flag(engine)))
+    call(_LIB, "td_mc_upsample", engine, dev, ptr(src), Cn, Hn, Wn, s, r0, c0, H, W, ptr(out))
     return out
 
 
@@ -154,11 +106,8 @@ def _finish(engine, dev, elev, padded, climate, H, W, i0, j0, planes, noise_scal
     n_clim = 0 if climate is None else int(climate.shape[0])
     assert elev.stride(1) == 1 and (elev.is_contiguous() or elev.untyped_storage().data_ptr() == padded.untyped_storage().data_ptr())
     ep = ptr(elev) if elev.is_contiguous() else C.c_void_p(elev.data_ptr())    # a view of padded: ptr(padded) below orders it
-    with torch.cuda.device(dev):
-        check(lib().td_mc_finish(C.c_void_p(engine.stream), ep, elev.stride(0), ptr(padded), ptr(climate) if climate is not None else None, n_clim,
-                                 H, W, i0, j0, ptr(planes) if planes is not None else None, float(noise_scale), float(detail_px),
-                                 float(native_res), float(biome_px), ptr(elev_out) if elev_out is not None else None,
-                                 ptr(biome_out) if biome_out is not None else None, _sync_flag(engine)))
+    call(_LIB, "td_mc_finish", engine, dev, ep, elev.stride(0), ptr(padded), ptr(climate), n_clim, H, W, i0, j0, ptr(planes), float(noise_scale),
+         float(detail_px), float(native_res), float(biome_px), ptr(elev_out), ptr(biome_out))
 
 
 def _upsampled(world, i1, j1, i2, j2, s, H, W, engine):
@@ -266,8 +215,7 @@ def noise_planes(i0, j0, H, W, *, engine=None):
     engine = engine or get_engine(None)
     dev = torch.device("cuda", engine.device_id)
     out = torch.empty((7, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().td_mc_noise(C.c_void_p(engine.stream), H, W, int(i0), int(j0), ptr(out), _sync_flag(engine)))
+    call(_LIB, "td_mc_noise", engine, dev, H, W, int(i0), int(j0), ptr(out))
     return out
 
 
@@ -288,8 +236,7 @@ def minecraft_payload(elev, biome=None, *, engine=None):
         b = (biome.detach() if torch.is_tensor(biome) else torch.from_numpy(np.ascontiguousarray(biome))).to(device=dev, dtype=torch.int16)
         b = b.contiguous()
     out = torch.empty((2 if b is not None else 1) * H * W, dtype=torch.int16, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().td_mc_payload(C.c_void_p(engine.stream), ptr(e), ptr(b) if b is not None else None, H, W, ptr(out), _sync_flag(engine)))
+    call(_LIB, "td_mc_payload", engine, dev, ptr(e), ptr(b), H, W, ptr(out))
     body = out.cpu().numpy().astype("<i2", copy=False).tobytes()
     return body, {"X-Height": str(H), "X-Width": str(W), "X-Dtype": "int16-le"}
 

@@ -11,15 +11,14 @@ biome, flow and a caller-supplied rgb image are not supported (no caller of the 
 """
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import torch
 
-from ._lib import TdError
-from .engine import get_engine, ptr
+from ._lib import Library
+from ._plumbing import call, engine_for, f32
+from .engine import ptr
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtd_relief.so")
 _P = C.c_void_p
 _SIGS = {
     "td_relief_last_error": (C.c_char_p, []),
@@ -27,27 +26,8 @@ _SIGS = {
                                 C.c_double, C.c_int, C.c_double, _P, C.c_int]),
 }
 EXPORTS = tuple(_SIGS)
-_lib = None
-
-
-def lib():
-    """Loads libtd_relief.so; raises if it has not been built.  There is no CPU fallback."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TdError(f"{LIB_PATH} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). There is no CPU fallback.")
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(l, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = l
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise TdError(f"td_relief error {rc}: {lib().td_relief_last_error().decode()}")
+_LIB = Library("libtd_relief.so", _SIGS, "td_relief_last_error", "td_relief")
+LIB_PATH, lib, check = _LIB.path, _LIB.lib, _LIB.check
 
 DEFAULT_AZIMUTHS = (315.0, 45.0, 135.0, 225.0)
 MAX_RADIUS = 64   # relief_csrc/relief_kernels.hip RELIEF_MAX_RADIUS: sigma below 15.9
@@ -57,18 +37,24 @@ _TERRAIN_POINTS = ((0.00, (0.2, 0.2, 0.6)), (0.15, (0.0, 0.6, 1.0)), (0.25, (0.0
                    (0.50, (1.0, 1.0, 0.6)), (0.75, (0.5, 0.36, 0.33)), (1.00, (1.0, 1.0, 1.0)))
 
 
-@functools.lru_cache(maxsize=4)
-def terrain_lut(n=256):
-    """(n, 3) float32 RGB rows of the terrain colormap, as matplotlib's lookup-table builder forms them (float64, clipped to [0, 1])."""
-    pos = np.array([p for p, _ in _TERRAIN_POINTS], dtype=np.float64) * (n - 1)
+def _segment_lut(pos, colors, n=256):
+    """(n, 3) float32 rows of a piecewise-linear colormap through `colors` at `pos`, as matplotlib's lookup-table builder forms them
+    (float64, clipped to [0, 1])."""
+    x = np.asarray(pos, dtype=np.float64) * (n - 1)
     xind = (n - 1) * np.linspace(0, 1, n)
-    ind = np.searchsorted(pos, xind)[1:-1]
+    ind = np.searchsorted(x, xind)[1:-1]
+    distance = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
     lut = np.empty((n, 3), dtype=np.float64)
     for c in range(3):
-        y = np.array([rgb[c] for _, rgb in _TERRAIN_POINTS], dtype=np.float64)
-        distance = (xind[1:-1] - pos[ind - 1]) / (pos[ind] - pos[ind - 1])
+        y = np.array([rgb[c] for rgb in colors], dtype=np.float64)
         lut[:, c] = np.concatenate([[y[0]], distance * (y[ind] - y[ind - 1]) + y[ind - 1], [y[-1]]])
-    out = np.clip(lut, 0.0, 1.0).astype(np.float32)
+    return np.clip(lut, 0.0, 1.0).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=4)
+def terrain_lut(n=256):
+    """(n, 3) read-only float32 RGB rows of the terrain colormap."""
+    out = _segment_lut([p for p, _ in _TERRAIN_POINTS], [rgb for _, rgb in _TERRAIN_POINTS], n)
     out.flags.writeable = False
     return out
 
@@ -132,10 +118,9 @@ def _enqueue(engine, e, out, fill, azimuth, sigma_large, sigma_small, resolution
     H, W = int(e.shape[0]), int(e.shape[1])
     lut, wl, rl, ws, rs = _device_tables(engine.device_id, float(sigma_large), float(sigma_small))
     has_range = vmin is not None and vmax is not None
-    with torch.cuda.device(e.device):
-        check(lib().td_relief_map(C.c_void_p(engine.stream), ptr(e), H, W, ptr(lut), ptr(wl), rl, ptr(ws), rs, float(azimuth), float(resolution),
-                                  float(relief), int(has_range), float(vmin) if has_range else 0.0, float(vmax) if has_range else 0.0,
-                                  int(fill is not None), float(fill) if fill is not None else 0.0, ptr(out), 0 if engine._async else 1))
+    call(_LIB, "td_relief_map", engine, e.device, ptr(e), H, W, ptr(lut), ptr(wl), rl, ptr(ws), rs, float(azimuth), float(resolution), float(relief),
+         int(has_range), float(vmin) if has_range else 0.0, float(vmax) if has_range else 0.0, int(fill is not None),
+         float(fill) if fill is not None else 0.0, ptr(out))
 
 
 @torch.no_grad()
@@ -147,10 +132,8 @@ def relief_map(elev, *, azimuths=DEFAULT_AZIMUTHS, sigma_large=6.0, sigma_small=
     a second sync for the fill value)."""
     _check_shape(elev.shape)
     H, W = int(elev.shape[0]), int(elev.shape[1])
-    if engine is None:
-        engine = get_engine(elev.device if (torch.is_tensor(elev) and elev.is_cuda) else None)
-    dev = torch.device("cuda", engine.device_id)
-    e = torch.as_tensor(elev).to(device=dev, dtype=torch.float32).contiguous()
+    engine, dev = engine_for(elev, engine)
+    e = f32(elev, dev)
     az = float(azimuths[0]) if isinstance(azimuths, (tuple, list)) and len(azimuths) > 0 else 315.0
     has_fill = bool(torch.isnan(e).any())
     fill = _nanmedian(e) if has_fill else None
@@ -166,10 +149,7 @@ def get_relief_map(elevation, climate, biome, flow, *, azimuths=DEFAULT_AZIMUTHS
     for name, value in (("biome", biome), ("flow", flow), ("rgb", rgb)):
         if value is not None:
             raise NotImplementedError(f"get_relief_map: `{name}` is not supported (only None)")
-    if torch.is_tensor(elevation):
-        e = elevation.detach()
-    else:
-        e = torch.from_numpy(np.ascontiguousarray(np.asarray(elevation), dtype=np.float32))
+    e = elevation.detach() if torch.is_tensor(elevation) else np.asarray(elevation)
     _check_shape(e.shape)
     out = relief_map(e, azimuths=azimuths, sigma_large=sigma_large, sigma_small=sigma_small, resolution=resolution, relief=relief,
                      vmin=vmin, vmax=vmax, engine=engine)

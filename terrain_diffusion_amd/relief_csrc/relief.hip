@@ -1,29 +1,11 @@
 // libtd_relief.so: the C-ABI of include/td_relief.h over the two kernels of relief_kernels.hip.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <string>
 
+#include "../side_csrc/td_side_host.h"
 #include "../../include/td_relief.h"
 #include "relief_kernels.hip"
 
 using namespace td;
-
-namespace {
-enum { OK = 0, ERR_ARG = -1, ERR_HIP = -2 };
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define RELIEF_HIP_TRY(expr)                                                                                     \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return fail(ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-    } while (0)
-
-bool is_device_ptr(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-}  // namespace
 
 extern "C" {
 
@@ -42,7 +24,7 @@ int td_relief_map(void* hip_stream, const float* elev, int H, int W, const float
     const size_t npx = (size_t)H * W;
     // scratch: the two axis-0-blurred planes and the two range words, from the stream-ordered pool
     void* scratch = nullptr;
-    RELIEF_HIP_TRY(hipMallocAsync(&scratch, 2 * npx * 4 + 256, st));
+    TD_HIP_TRY(hipMallocAsync(&scratch, 2 * npx * 4 + 256, st));
     float* bl = (float*)scratch;
     float* bs = bl + npx;
     unsigned* range_bits = has_range ? nullptr : (unsigned*)(bs + npx);
@@ -70,11 +52,7 @@ int td_relief_map(void* hip_stream, const float* elev, int H, int W, const float
                            (const unsigned*)range_bits, p, out);
         err = hipGetLastError();
     }
-    const hipError_t ferr = hipFreeAsync(scratch, st);   // back to the pool behind the two kernels
-    RELIEF_HIP_TRY(err);
-    RELIEF_HIP_TRY(ferr);
-    if (synchronize) RELIEF_HIP_TRY(hipStreamSynchronize(st));
-    return OK;
+    return finish(st, scratch, err, synchronize);   // the scratch goes back to the pool behind the two kernels
 }
 
 }  // extern "C"

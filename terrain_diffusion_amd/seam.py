@@ -5,14 +5,10 @@ window outputs through td_seam_exchange_windows instead — ONE grouped ncclSend
 The library is separate from libtd_engine.so so that the engine carries no RCCL dependency.  No fallback: a missing library raises.
 """
 import ctypes as C
-import os
 
 import torch
 
-from ._lib import TdError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libtd_seam.so")
+from ._lib import Library, TdError
 
 OWN, NEEDED, SENDS, RECVS = 0, 1, 2, 3
 ID_BYTES = 128
@@ -44,25 +40,14 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS)
 
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TdError(f"{LIB_PATH} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). There is no fallback.")
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            f = getattr(l, name)
-            f.restype, f.argtypes = res, args
-        _lib = l
-    return _lib
+_LIB = Library("libtd_seam.so", _SIGS, "td_seam_last_error", "libtd_seam", missing="There is no fallback.")
+LIB_PATH, lib = _LIB.path, _LIB.lib
 
 
 def check(code):
+    """Negative codes raise; counts and sizes come back."""
     if code < 0:
-        raise TdError(f"libtd_seam: {lib().td_seam_last_error().decode()} (code {code})")
+        raise TdError(f"libtd_seam: {_LIB.error_text()} (code {code})")
     return code
 
 
@@ -80,8 +65,8 @@ class CShardPlan:
         self.regions = [self._region(r) for r in range(world)]
 
     def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.td_seam_plan_destroy(self._h)
+        if getattr(self, "_h", None) and _LIB.handle is not None:
+            _LIB.handle.td_seam_plan_destroy(self._h)
             self._h = None
 
     def _starts(self, axis):

@@ -108,12 +108,13 @@ def test_bad_shapes_are_refused(shape):
 
 def test_there_is_no_cpu_fallback(monkeypatch):
     """Without the library every call raises: nothing computes on the host."""
-    from terrain_diffusion_amd import hydrology
+    from terrain_diffusion_amd import explorer, hydrology, minecraft, relief
     from terrain_diffusion_amd._lib import TdError
-    monkeypatch.setattr(hydrology, "_lib", None)
-    monkeypatch.setattr(hydrology, "LIB_PATH", "/nonexistent/libtd_hydro.so")
-    with pytest.raises(TdError, match="no CPU fallback"):
-        hydrology.lib()
+    for module in (relief, hydrology, minecraft, explorer):
+        monkeypatch.setattr(module._LIB, "handle", None)
+        monkeypatch.setattr(module._LIB, "path", "/nonexistent/" + module.LIB_PATH.rsplit("/", 1)[1])
+        with pytest.raises(TdError, match="no CPU fallback"):
+            module.lib()
     z = np.full((6, 7), 10.0, np.float32)
     rr, cc = np.zeros((6, 7), np.int64), np.zeros((6, 7), np.int64)
     calls = (lambda: hydrology.d8_flow(z), lambda: hydrology.flow_accumulation(z, rr, cc, np.ones((6, 7), bool)),
