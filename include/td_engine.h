@@ -70,7 +70,7 @@ void* td_engine_stream(td_engine* e);
  * torch.cuda.Stream that also carries the caller's own kernels and its RCCL transfers; NOT the legacy NULL stream, which cannot be captured
  * into the engine's hipGraphs); NULL restores the engine's own stream.  The old stream is drained first.  By default every call still returns
  * with its results complete; with td_engine_set_option(e, "async", 1) a call whose DATA buffers are all device pointers (td_sample_edm*,
- * td_sample_consistency*, td_noise_patches, td_gather_regions, td_blend_windows, td_blend_normalize, td_resample2d, td_residual_plus,
+ * td_sample_consistency*, td_sample_grid_batch, td_cond_rows, td_noise_patches, td_gather_regions, td_blend_windows, td_blend_normalize, td_resample2d, td_residual_plus,
  * td_elev_finish, td_climate_finish, td_ddim_cfg_step) only ENQUEUES its work, ordered with whatever else the caller puts on that stream.
  * The small host arrays such calls take (origins, descriptors, tap tables, timesteps) are copied into a pinned ring inside the call, so the
  * caller may reuse them on return; device buffers must stay valid in STREAM order (a torch tensor released on that stream is).  Per-call
@@ -84,7 +84,9 @@ int td_engine_set_stream(td_engine* e, void* hip_stream);
  *   "batch_invariant"=0/1 (a window's result does not depend on the batch / GPU it rides in: no split-K, LDS-DMA conv flavour pinned),
  *   "solver_order"=1/2/3 and "lower_order_final"=0/1 (EDMDPMSolverMultistepScheduler.config), "fuse_solver"=0/1 (solver update in the
  *   output conv's epilogue), "dual_stream"=0/1 (default 1) + "dual_stream_min_batch" (default 32: batches at least that large run as two concurrent half-batch lanes), "plan_cache_mb", "plan_cache_max",
- *   "sampler_stop_after"=-1/k (test read-back, default -1 = off: td_sample_edm* enqueue only the first min(k, n_steps) steps of the n_steps-step run).
+ *   "sampler_stop_after"=-1/k (test read-back, default -1 = off: td_sample_edm* enqueue only the first min(k, n_steps) steps of the n_steps-step run),
+ *   "grid_fused"=1/0 (default 1; read by the host samplers, not by the engine: a window batch of the grid sampler is ONE td_sample_grid_batch call / the
+ *   four calls td_noise_patches, conditioning rows on the host, td_sample_edm, td_blend_windows -- same bits, the A/B arm of the one-call path).
  * Plan builder (speed only; every one is part of the plan-cache key):
  *   "glds", "glds_min_wgs", "glds_bn64", "glds_round_aware", "glds_small_max_groups", "glds_dma1x1", "glds_tiny", "bn128_min_wgs",
  *   "splitk", "splitk_target_wgs", "splitk_weighted", "glds_splitk", "glds_splitk_from_groups", "glds_splitk_max", "glds_splitk_min_groups",
@@ -99,6 +101,8 @@ int td_engine_set_stream(td_engine* e, void* hip_stream);
  *   conv_fewcout.hip instead of a 64-cout MFMA tile).
  * Test hooks that force a tile shape wherever it is legal: "glds_variant"=-1/0/1, "glds_bn"=0/64/96/128, "sb_mt"=0/1/2/4, "sb_nt"=0/1/2. */
 int td_engine_set_option(td_engine* e, const char* key, int64_t value);
+/* the value td_engine_set_option stored for `key`, or `dflt` when it was never set (the engine's own defaults live where each option is read) */
+int64_t td_engine_get_option(td_engine* e, const char* key, int64_t dflt);
 
 /* With option "profile"=1 the samplers run eagerly (no graph) with HIP events recorded on the engine stream around every
  * conv launch (and every other U-Net kernel); this reads/reset the accumulated kernel time and launch counts. */
@@ -181,6 +185,53 @@ int td_sample_edm_img(td_unet* u, int n, int H, int W, int n_steps, const float*
                       const float* cond_img, int cimg_channels, float* x);
 int td_sample_consistency_img(td_unet* u, int n, int H, int W, float t, float sigma_data, const float* sample, const float* z,
                               const float* cond, const float* cond_img, int cimg_channels, float* out);
+
+/* ---- conditioning rows (sample_diffusion_base.py:11-48, process_cond_img) -------------------------------------
+ * The 16 + 16 + 4 + 16 + n_hist + 1 conditioning floats of n windows of ONE conditioning grid in one launch.  grid: (7, grid_rows, grid_cols) fp32, host or
+ * device; window i reads the 4 x 4 cells at (pos_host[2i], pos_host[2i+1]) (host int32 pairs, inside the grid).  Per window, bit for bit what the
+ * reference function returns for that (1,7,4,4) patch: v = (x - mean_c) / std_c, NaN -> means[0] (a batch of one: the reference's [0:1] fill covers every
+ * channel, so its RNG fill of NaN climate means is never drawn), +-inf -> +-FLT_MAX; row = [channel 0 | channel 1 | mean of channels 2..5 over cells
+ * [1:3,1:3] | channel 6 | hist_host (n_hist floats) | (noise_level - 0.5) * sqrt(12)], each part scaled by Cc / sqrt(len) / 6 with
+ * Cc = sqrt(total_len * 6).  means_host / stds_host: 7 floats.  out: [n][53 + n_hist] fp32, host or device.  Enqueue-only under "async" when grid and
+ * out are device buffers. */
+int td_cond_rows(td_engine* e, const float* grid, int grid_rows, int grid_cols, int n, const int32_t* pos_host, const float* means_host,
+                 const float* stds_host, const float* hist_host, int n_hist, float noise_level, float* out);
+
+/* ---- one window batch of the tiled sampler as one call ------------------------------------------------------------
+ * The batch loop body of sample_base_diffusion (sample_diffusion_base.py:115-168) for n windows: initial noise (td_noise_patches: seed, origins, tile
+ * size, scale = sigma_0) -> conditioning rows (td_cond_rows from `cond_grid`, or ready `cond_rows` [n][cond_row_len], host or device, when that is not
+ * NULL) -> td_sample_edm (both lanes, the captured graph) -> td_blend_windows into `canvas`.  All host preparation and every upload happen first; the GPU
+ * work is then enqueued back to back on the engine's stream and the call ends ONCE: complete on return by default, enqueue-only under "async" (device
+ * grid / rows).  Same kernels, inputs and order as the four separate calls: windows and canvas are bit-identical to theirs.
+ * canvas: device (C+1, Hc, Wc) with the blend geometry of td_blend_windows (wi_host / wj_host: n entries; H = W = size), or NULL for no blend;
+ * windows_out: optional device [n][C][H][W] that receives the pre-blend windows (required when canvas is NULL).  Models without conditioning-image
+ * channels only; autoguidance stays on td_sample_edm_guided. */
+typedef struct td_grid_batch {
+    uint64_t noise_seed;
+    int32_t n, H, W, tile_h, tile_w;
+    float noise_scale;
+    const int64_t* origins_host;           /* n (y0, x0) pairs */
+    const float* cond_rows;                /* ready rows, or NULL: rows from cond_grid */
+    const float* cond_grid;                /* (7, grid_rows, grid_cols), host or device */
+    int32_t grid_rows, grid_cols;
+    const int32_t* cond_pos_host;          /* n (i, j) pairs */
+    const float* cond_means_host;
+    const float* cond_stds_host;
+    const float* hist_host;
+    int32_t n_hist;
+    float noise_level;
+    int32_t n_steps;
+    float sigma_data;
+    const float* sigmas_host;              /* n_steps + 1 */
+    float* canvas;
+    int32_t Hc, Wc, size, n_rows, n_cols, accumulate;
+    const int32_t* row_starts_host;
+    const int32_t* col_starts_host;
+    const int32_t* wi_host;
+    const int32_t* wj_host;
+    float* windows_out;
+} td_grid_batch;
+int td_sample_grid_batch(td_unet* u, const td_grid_batch* batch);
 
 /* ---- overlap blend (sample_diffusion_base.py:164-168; annotated_infinite_panorama.py:145-150) ----------------
  * canvas: (C+1, Hc, Wc) fp32, weighted sums + weight channel.  Adds window i (tiles[i] = [C][size][size]) at

@@ -52,6 +52,18 @@ class UnetConfig(C.Structure):
 
 
 _P = C.c_void_p
+
+
+class GridBatch(C.Structure):
+    """td_grid_batch (include/td_engine.h): one window batch of the tiled sampler for td_sample_grid_batch"""
+    _fields_ = [("noise_seed", C.c_uint64), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("tile_h", C.c_int32), ("tile_w", C.c_int32),
+                ("noise_scale", C.c_float), ("origins_host", _P), ("cond_rows", _P), ("cond_grid", _P), ("grid_rows", C.c_int32), ("grid_cols", C.c_int32),
+                ("cond_pos_host", _P), ("cond_means_host", _P), ("cond_stds_host", _P), ("hist_host", _P), ("n_hist", C.c_int32), ("noise_level", C.c_float),
+                ("n_steps", C.c_int32), ("sigma_data", C.c_float), ("sigmas_host", _P), ("canvas", _P), ("Hc", C.c_int32), ("Wc", C.c_int32),
+                ("size", C.c_int32), ("n_rows", C.c_int32), ("n_cols", C.c_int32), ("accumulate", C.c_int32), ("row_starts_host", _P),
+                ("col_starts_host", _P), ("wi_host", _P), ("wj_host", _P), ("windows_out", _P)]
+
+
 _SIGS = {
     "td_last_error": (C.c_char_p, []),
     "td_version": (C.c_int, []),
@@ -62,6 +74,7 @@ _SIGS = {
     "td_engine_stream": (_P, [_P]),
     "td_engine_set_stream": (C.c_int, [_P, _P]),
     "td_engine_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "td_engine_get_option": (C.c_int64, [_P, C.c_char_p, C.c_int64]),
     "td_engine_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "td_engine_profile_read_glds": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "td_engine_profile_dump": (C.c_int, [_P, C.c_char_p, C.c_int64]),
@@ -79,6 +92,8 @@ _SIGS = {
     "td_tile_seed": (C.c_uint64, [C.c_uint64, C.c_int64, C.c_int64]),
     "td_standard_normal": (C.c_int, [_P, C.c_uint64, C.c_int64, _P]),
     "td_noise_patches": (C.c_int, [_P, C.c_uint64, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
+    "td_cond_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_float, _P]),
+    "td_sample_grid_batch": (C.c_int, [_P, C.POINTER(GridBatch)]),
     "td_sample_edm": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P]),
     "td_sample_edm_guided": (C.c_int, [_P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P]),
     "td_sample_consistency": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P]),

@@ -1299,7 +1299,7 @@ int td_engine_set_stream(td_engine* e, void* hip_stream) {
 static const char* const kKnownOptions[] = {
     // behaviour
     "async", "batch_invariant", "fuse_solver", "graph", "lower_order_final", "profile", "solver_order", "dual_stream", "dual_stream_min_batch", "sampler_stop_after",
-    "plan_cache_mb", "plan_cache_max",
+    "plan_cache_mb", "plan_cache_max", "grid_fused",
     // plan builder (speed only, or test hooks that force a tile shape; all part of the plan-cache key)
     "attn_mfma", "bn128_min_wgs", "glds", "glds_bn", "glds_bn64", "glds_dma1x1", "glds_min_wgs", "glds_round_aware", "glds_small_max_groups",
     "glds_splitk", "glds_splitk_from_groups", "glds_splitk_max", "glds_splitk_min_groups", "glds_tiny", "glds_variant", "glds_wide", "glds_wide_min_wgs", "glds_wide_tail", "glds_wide_persist", "fewcout",
@@ -1313,6 +1313,8 @@ int td_engine_set_option(td_engine* e, const char* key, int64_t value) {
     e->opt[key] = value;
     return TD_OK;
 }
+
+int64_t td_engine_get_option(td_engine* e, const char* key, int64_t dflt) { return (e && key) ? e->option(key, dflt) : dflt; }
 
 int td_engine_profile_read(td_engine* e, double* conv_ms, int64_t* conv_launches, double* other_ms, int64_t* other_launches, int reset) {
     if (conv_ms) *conv_ms = e->prof_conv_ms;
@@ -1702,19 +1704,16 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
 // The second lane's stream is ordered behind the first lane's at entry (inputs produced on the engine's stream -- the caller's, with
 // td_engine_set_stream -- are complete before lane two reads them) and the first lane's stream waits for the second at the end, so that the call ends
 // like a single-lane one: results ordered on the engine's stream, enqueue-only under option "async".
-static int sample_edm_impl(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
-                           const float* cond, const float* cond_img, int cimg, float* x) {
+// The sampler's body, enqueue-only: one lane or two on the engine's streams, ending ordered on e->stream.  On failure both streams are drained.
+static int sample_edm_enqueue(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
+                              const float* cond, const float* cond_img, int cimg, float* x, std::vector<Buf>& hold) {
     td_engine* e = u->eng;
-    DevGuard dg_(e->device);
-    std::vector<Buf> hold;
     const bool dual = e->stream2 && e->option("dual_stream", 1) != 0 && n >= std::max<int64_t>(2, e->option("dual_stream_min_batch", 32));
     const bool concurrent = e->option("profile", 0) == 0;  // profile mode times every launch with events on ONE stream: the lanes run one after the other
-    const bool all_dev = is_device_ptr(x) && (!cond || is_device_ptr(cond)) && (!cond_img || is_device_ptr(cond_img));
     if (!dual) {
         int rc = sample_edm_lane(u, guide, gscale, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, 0, hold);
-        if (rc) { (void)hipStreamSynchronize(e->stream); return rc; }
-        // default: results complete on return (the caller's framework uses other streams); option "async": left enqueued on e->stream
-        return end_call(e, hold, all_dev);
+        if (rc) (void)hipStreamSynchronize(e->stream);
+        return rc;
     }
     const int nA = n / 2, nB = n - nA, C = u->cfg.out_channels;
     const size_t HW = (size_t)H * W;
@@ -1728,6 +1727,18 @@ static int sample_edm_impl(td_unet* u, td_unet* guide, float gscale, int n, int 
     }
     if (rc) { (void)hipStreamSynchronize(e->stream); (void)hipStreamSynchronize(e->stream2); return rc; }
     if (concurrent) { HIP_TRY(hipEventRecord(e->ev_join, e->stream2)); HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join, 0)); }
+    return TD_OK;
+}
+
+static int sample_edm_impl(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
+                           const float* cond, const float* cond_img, int cimg, float* x) {
+    td_engine* e = u->eng;
+    DevGuard dg_(e->device);
+    std::vector<Buf> hold;
+    const bool all_dev = is_device_ptr(x) && (!cond || is_device_ptr(cond)) && (!cond_img || is_device_ptr(cond_img));
+    int rc = sample_edm_enqueue(u, guide, gscale, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, hold);
+    if (rc) return rc;
+    // default: results complete on return (the caller's framework uses other streams); option "async": left enqueued on e->stream
     return end_call(e, hold, all_dev);
 }
 
@@ -1808,15 +1819,21 @@ int td_standard_normal(td_engine* e, uint64_t seed, int64_t n, float* out) {
 
 static inline int64_t fdiv(int64_t a, int64_t b) { int64_t q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
 
-int td_noise_patches(td_engine* e, uint64_t base_seed, int n_windows, const int64_t* origins, int h, int w, int channels, int tile_h, int tile_w,
-                     float scale, float* out) {
-    DevGuard dg_(e->device);
-    if (n_windows <= 0) return TD_OK;
+// td_noise_patches in two halves: host preparation with its uploads, and the two launches.  NoiseJob owns the host arrays the uploads read
+// (they have to outlive a copy that has not run yet) and the device scratch.
+struct NoiseJob {
+    std::vector<uint64_t> seeds;
+    std::vector<int> index, org;
+    Buf dseeds, dtiles, dindex, dorg;
+    int64_t tn = 0;
+};
+static int noise_prepare(td_engine* e, NoiseJob& j, uint64_t base_seed, int n_windows, const int64_t* origins, int h, int w, int channels, int tile_h, int tile_w) {
     if (h > tile_h || w > tile_w) return fail(TD_ERR_UNSUPPORTED, "window larger than the noise tile");
     // unique noise tiles touched by the windows
     std::map<std::pair<int64_t, int64_t>, int> slot;
-    std::vector<uint64_t> seeds;
-    std::vector<int> index((size_t)n_windows * 4, 0), org((size_t)n_windows * 2);
+    std::vector<uint64_t>& seeds = j.seeds;
+    std::vector<int>& index = j.index; std::vector<int>& org = j.org;
+    index.assign((size_t)n_windows * 4, 0); org.resize((size_t)n_windows * 2);
     for (int i = 0; i < n_windows; ++i) {
         const int64_t y0 = origins[2 * i], x0 = origins[2 * i + 1];
         org[2 * i] = (int)y0; org[2 * i + 1] = (int)x0;
@@ -1830,21 +1847,35 @@ int td_noise_patches(td_engine* e, uint64_t base_seed, int n_windows, const int6
                 index[(size_t)i * 4 + (ty - ty0) * 2 + (tx - tx0)] = s;
             }
     }
-    const int64_t tn = (int64_t)channels * tile_h * tile_w;
-    Buf dseeds(new DevBuf()), dtiles(new DevBuf()), dindex(new DevBuf()), dorg(new DevBuf());
-    HIP_TRY(dseeds->scratch(e->scratch, seeds.size() * 8)); HIP_TRY(dtiles->scratch(e->scratch, seeds.size() * tn * 4));
-    HIP_TRY(dindex->scratch(e->scratch, index.size() * 4)); HIP_TRY(dorg->scratch(e->scratch, org.size() * 4));
-    hipStream_t st = e->stream;
+    j.tn = (int64_t)channels * tile_h * tile_w;
+    j.dseeds.reset(new DevBuf()); j.dtiles.reset(new DevBuf()); j.dindex.reset(new DevBuf()); j.dorg.reset(new DevBuf());
+    HIP_TRY(j.dseeds->scratch(e->scratch, seeds.size() * 8)); HIP_TRY(j.dtiles->scratch(e->scratch, seeds.size() * j.tn * 4));
+    HIP_TRY(j.dindex->scratch(e->scratch, index.size() * 4)); HIP_TRY(j.dorg->scratch(e->scratch, org.size() * 4));
     int rc;
-    if ((rc = upload(e, dseeds->p, seeds.data(), seeds.size() * 8)) || (rc = upload(e, dindex->p, index.data(), index.size() * 4)) ||
-        (rc = upload(e, dorg->p, org.data(), org.size() * 4))) return rc;
+    if ((rc = upload(e, j.dseeds->p, seeds.data(), seeds.size() * 8)) || (rc = upload(e, j.dindex->p, index.data(), index.size() * 4)) ||
+        (rc = upload(e, j.dorg->p, org.data(), org.size() * 4))) return rc;
+    return TD_OK;
+}
+static int noise_enqueue(td_engine* e, const NoiseJob& j, int n_windows, int h, int w, int channels, int tile_h, int tile_w, float scale, float* out_dev) {
+    hipStream_t st = e->stream;
+    hipLaunchKernelGGL(noise_tiles_kernel, dim3((unsigned)j.seeds.size()), dim3(256), 0, st, (const uint64_t*)j.dseeds->p, (float*)j.dtiles->p, j.tn);
+    hipLaunchKernelGGL(noise_gather_kernel, dim3((channels * h * w + 255) / 256, n_windows), dim3(256), 0, st, (const float*)j.dtiles->p, (const int*)j.dindex->p,
+                       (const int*)j.dorg->p, out_dev, channels, h, w, tile_h, tile_w, scale);
+    HIP_TRY(hipGetLastError());
+    return TD_OK;
+}
+
+int td_noise_patches(td_engine* e, uint64_t base_seed, int n_windows, const int64_t* origins, int h, int w, int channels, int tile_h, int tile_w,
+                     float scale, float* out) {
+    DevGuard dg_(e->device);
+    if (n_windows <= 0) return TD_OK;
+    NoiseJob j;
+    int rc;
+    if ((rc = noise_prepare(e, j, base_seed, n_windows, origins, h, w, channels, tile_h, tile_w))) return rc;
     std::vector<Buf> hold;
     OutStage os;
     if ((rc = out_device(e, out, (size_t)n_windows * channels * h * w * 4, hold, &os))) return rc;
-    hipLaunchKernelGGL(noise_tiles_kernel, dim3((unsigned)seeds.size()), dim3(256), 0, st, (const uint64_t*)dseeds->p, (float*)dtiles->p, tn);
-    hipLaunchKernelGGL(noise_gather_kernel, dim3((channels * h * w + 255) / 256, n_windows), dim3(256), 0, st, (const float*)dtiles->p, (const int*)dindex->p,
-                       (const int*)dorg->p, (float*)os.dev, channels, h, w, tile_h, tile_w, scale);
-    HIP_TRY(hipGetLastError());
+    if ((rc = noise_enqueue(e, j, n_windows, h, w, channels, tile_h, tile_w, scale, (float*)os.dev))) return rc;
     if ((rc = out_finish(e, os))) return rc;
     return end_call(e, hold, !os.host);
 }
@@ -1873,12 +1904,17 @@ int td_linear_weight_window(td_engine* e, int size, float* out) {
     return TD_OK;
 }
 
-int td_blend_windows(td_engine* e, float* canvas, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols,
-                     const int32_t* col_starts, int n_tiles, const int32_t* wi, const int32_t* wj, const float* tiles, int accumulate) {
-    DevGuard dg_(e->device);
+// td_blend_windows in two halves, like the noise: the row / column / slot maps with their six uploads, and the launch.
+struct BlendJob {
+    std::vector<int> rowmap, colmap, tile_of;
+    std::vector<float> ww;
+    Buf drow, dcol, drs, dcs, dtof, dww;
+};
+static int blend_prepare(td_engine* e, BlendJob& j, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols, const int32_t* col_starts,
+                         int n_tiles, const int32_t* wi, const int32_t* wj) {
     if (C + 1 > 8) return fail(TD_ERR_UNSUPPORTED, "C+1 must be <= 8");
-    hipStream_t st = e->stream;
-    std::vector<int> rowmap((size_t)Hc * 4, -1), colmap((size_t)Wc * 4, -1), tile_of((size_t)n_rows * n_cols, -1);
+    std::vector<int>& rowmap = j.rowmap; std::vector<int>& colmap = j.colmap; std::vector<int>& tile_of = j.tile_of;
+    rowmap.assign((size_t)Hc * 4, -1); colmap.assign((size_t)Wc * 4, -1); tile_of.assign((size_t)n_rows * n_cols, -1);
     for (int ic = 0; ic < n_rows; ++ic)
         for (int y = std::max(0, row_starts[ic]); y < std::min(Hc, row_starts[ic] + size); ++y) {
             int k = 0;
@@ -1897,18 +1933,32 @@ int td_blend_windows(td_engine* e, float* canvas, int C, int Hc, int Wc, int siz
         if (wi[i] < 0 || wi[i] >= n_rows || wj[i] < 0 || wj[i] >= n_cols) return fail(TD_ERR_ARG, "window index out of range");
         tile_of[(size_t)wi[i] * n_cols + wj[i]] = i;
     }
-    std::vector<float> ww;
-    weight_window_host(size, ww);
+    weight_window_host(size, j.ww);
     auto up = [&](const void* src, size_t bytes, Buf& b) -> int {
         b.reset(new DevBuf());
         HIP_TRY(b->scratch(e->scratch, bytes));
         return upload(e, b->p, src, bytes);
     };
-    Buf drow, dcol, drs, dcs, dtof, dww;
     int rc;
-    if ((rc = up(rowmap.data(), rowmap.size() * 4, drow)) || (rc = up(colmap.data(), colmap.size() * 4, dcol)) || (rc = up(row_starts, (size_t)n_rows * 4, drs)) ||
-        (rc = up(col_starts, (size_t)n_cols * 4, dcs)) || (rc = up(tile_of.data(), tile_of.size() * 4, dtof)) || (rc = up(ww.data(), ww.size() * 4, dww)))
+    if ((rc = up(rowmap.data(), rowmap.size() * 4, j.drow)) || (rc = up(colmap.data(), colmap.size() * 4, j.dcol)) || (rc = up(row_starts, (size_t)n_rows * 4, j.drs)) ||
+        (rc = up(col_starts, (size_t)n_cols * 4, j.dcs)) || (rc = up(tile_of.data(), tile_of.size() * 4, j.dtof)) || (rc = up(j.ww.data(), j.ww.size() * 4, j.dww)))
         return rc;
+    return TD_OK;
+}
+static int blend_enqueue(td_engine* e, const BlendJob& j, float* dcanvas, int C, int Hc, int Wc, int size, int n_cols, const float* dtiles, int accumulate) {
+    hipLaunchKernelGGL(blend_gather_kernel, grid1((size_t)Hc * Wc), dim3(256), 0, e->stream, dtiles, (const float*)j.dww->p, dcanvas, C, Hc, Wc, size,
+                       (const int*)j.drow->p, (const int*)j.dcol->p, (const int*)j.drs->p, (const int*)j.dcs->p, (const int*)j.dtof->p, n_cols, accumulate);
+    HIP_TRY(hipGetLastError());
+    return TD_OK;
+}
+
+int td_blend_windows(td_engine* e, float* canvas, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols,
+                     const int32_t* col_starts, int n_tiles, const int32_t* wi, const int32_t* wj, const float* tiles, int accumulate) {
+    DevGuard dg_(e->device);
+    hipStream_t st = e->stream;
+    BlendJob j;
+    int rc;
+    if ((rc = blend_prepare(e, j, C, Hc, Wc, size, n_rows, row_starts, n_cols, col_starts, n_tiles, wi, wj))) return rc;
     std::vector<Buf> hold;
     const void* dt;
     if ((rc = to_device(e, tiles, (size_t)n_tiles * C * size * size * 4, hold, &dt))) return rc;
@@ -1922,9 +1972,7 @@ int td_blend_windows(td_engine* e, float* canvas, int C, int Hc, int Wc, int siz
         dcanvas = (float*)cstage->p;
         if (accumulate) HIP_TRY(hipMemcpyAsync(dcanvas, canvas, cbytes, hipMemcpyHostToDevice, st));
     }
-    hipLaunchKernelGGL(blend_gather_kernel, grid1((size_t)Hc * Wc), dim3(256), 0, st, (const float*)dt, (const float*)dww->p, dcanvas, C, Hc, Wc, size,
-                       (const int*)drow->p, (const int*)dcol->p, (const int*)drs->p, (const int*)dcs->p, (const int*)dtof->p, n_cols, accumulate);
-    HIP_TRY(hipGetLastError());
+    if ((rc = blend_enqueue(e, j, dcanvas, C, Hc, Wc, size, n_cols, (const float*)dt, accumulate))) return rc;
     if (!cdev) HIP_TRY(hipMemcpyAsync(canvas, dcanvas, cbytes, hipMemcpyDeviceToHost, st));
     return end_call(e, hold, cdev && is_device_ptr(tiles));
 }
@@ -1974,6 +2022,110 @@ int td_blend_normalize(td_engine* e, const float* canvas, int C, int Hc, int Wc,
     HIP_TRY(hipGetLastError());
     if ((rc = out_finish(e, os))) return rc;
     return end_call(e, hold, !os.host && is_device_ptr(canvas));
+}
+
+// ---- conditioning rows (sample_diffusion_base.py:11-48 per window, on the GPU)
+struct CondJob {
+    std::vector<int32_t> stage;   // 2 n window positions, then the nh histogram floats (one upload)
+    Buf dstage;
+    const void* dgrid = nullptr;
+    CondRowsParams p;
+};
+static int cond_prepare(td_engine* e, CondJob& j, const float* grid, int R, int Cg, int n, const int32_t* pos, const float* means, const float* stds,
+                        const float* hist, int nh, float noise_level, std::vector<Buf>& hold) {
+    if (!grid || !pos || !means || !stds || (nh > 0 && !hist)) return fail(TD_ERR_ARG, "td_cond_rows: null argument");
+    if (n < 1 || R < 4 || Cg < 4 || nh < 0 || nh > 4096) return fail(TD_ERR_ARG, "td_cond_rows: n >= 1, a grid of at least 4 x 4 cells, 0 <= nh <= 4096");
+    for (int i = 0; i < n; ++i)
+        if (pos[2 * i] < 0 || pos[2 * i] + 4 > R || pos[2 * i + 1] < 0 || pos[2 * i + 1] + 4 > Cg) return fail(TD_ERR_ARG, "td_cond_rows: window position outside the grid");
+    CondRowsParams& p = j.p;
+    for (int c = 0; c < 7; ++c) { p.mean[c] = means[c]; p.stdv[c] = stds[c]; }
+    // the host path's python-float arithmetic, in its order: Cc = sqrt(sum_L / (6 * (1/6)^2)), factor_L = Cc / sqrt(L) * (1/6), then one cast to fp32
+    const int L[6] = {16, 16, 4, 16, nh, 1};
+    const double inv = 1.0 / 6;
+    const double Cc = sqrt((double)(53 + nh) / (6 * pow(inv, 2.0)));
+    for (int k = 0; k < 6; ++k) p.factor[k] = L[k] > 0 ? (float)(Cc / sqrt((double)L[k]) * inv) : 0.f;
+    p.nan_fill = means[0];
+    p.noise_entry = (noise_level - 0.5f) * (float)sqrt(12.0);
+    p.R = R; p.Cg = Cg; p.nh = nh; p.n = n;
+    int rc;
+    if ((rc = to_device(e, grid, (size_t)7 * R * Cg * 4, hold, &j.dgrid))) return rc;
+    j.stage.resize((size_t)2 * n + nh);
+    memcpy(j.stage.data(), pos, (size_t)2 * n * 4);
+    if (nh) memcpy(j.stage.data() + (size_t)2 * n, hist, (size_t)nh * 4);
+    j.dstage.reset(new DevBuf());
+    HIP_TRY(j.dstage->scratch(e->scratch, j.stage.size() * 4));
+    return upload(e, j.dstage->p, j.stage.data(), j.stage.size() * 4);
+}
+static int cond_enqueue(td_engine* e, const CondJob& j, float* out_dev) {
+    const int32_t* d = (const int32_t*)j.dstage->p;
+    hipLaunchKernelGGL(cond_rows_kernel, grid1((size_t)j.p.n * (53 + j.p.nh)), dim3(256), 0, e->stream, (const float*)j.dgrid, (const int*)d,
+                       (const float*)(d + (size_t)2 * j.p.n), out_dev, j.p);
+    HIP_TRY(hipGetLastError());
+    return TD_OK;
+}
+
+int td_cond_rows(td_engine* e, const float* grid, int grid_rows, int grid_cols, int n, const int32_t* pos_host, const float* means_host, const float* stds_host,
+                 const float* hist_host, int n_hist, float noise_level, float* out) {
+    if (!e || !out) return fail(TD_ERR_ARG, "td_cond_rows: null argument");
+    DevGuard dg_(e->device);
+    std::vector<Buf> hold;
+    CondJob j;
+    int rc;
+    if ((rc = cond_prepare(e, j, grid, grid_rows, grid_cols, n, pos_host, means_host, stds_host, hist_host, n_hist, noise_level, hold))) return rc;
+    OutStage os;
+    if ((rc = out_device(e, out, (size_t)n * (53 + n_hist) * 4, hold, &os))) return rc;
+    if ((rc = cond_enqueue(e, j, (float*)os.dev))) return rc;
+    if ((rc = out_finish(e, os))) return rc;
+    return end_call(e, hold, !os.host && is_device_ptr(grid));
+}
+
+// ---- one window batch of the grid sampler as ONE call: every host preparation and upload first, then noise -> conditioning rows -> the sampler's
+// lanes -> blend accumulate enqueued back to back on the engine's stream, and one end_call.  The same kernels on the same inputs in the same order as
+// td_noise_patches + td_cond_rows + td_sample_edm + td_blend_windows, which wait for the stream four times and leave the GPU idle in between.
+int td_sample_grid_batch(td_unet* u, const td_grid_batch* b) {
+    if (!u || !b) return fail(TD_ERR_ARG, "td_sample_grid_batch: null argument");
+    td_engine* e = u->eng;
+    DevGuard dg_(e->device);
+    if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
+    const int n = b->n, H = b->H, W = b->W, C = u->cfg.out_channels;
+    if (n < 1 || H < 1 || W < 1 || !b->origins_host || !b->sigmas_host || b->n_steps < 1) return fail(TD_ERR_ARG, "td_sample_grid_batch: bad batch description");
+    if (u->cfg.in_channels != C) return fail(TD_ERR_ARG, "td_sample_grid_batch: models with conditioning-image channels take td_sample_edm_img");
+    if (!b->canvas && !b->windows_out) return fail(TD_ERR_ARG, "td_sample_grid_batch: neither a canvas nor a window buffer to write to");
+    if ((b->canvas && !is_device_ptr(b->canvas)) || (b->windows_out && !is_device_ptr(b->windows_out))) return fail(TD_ERR_ARG, "td_sample_grid_batch: canvas and window buffer are device buffers");
+    if (b->canvas && (H != b->size || W != b->size)) return fail(TD_ERR_ARG, "td_sample_grid_batch: the blend takes square windows of `size`");
+    if (u->cond_row_len > 0 && !b->cond_rows && !b->cond_grid) return fail(TD_ERR_ARG, "td_sample_grid_batch: the model takes conditioning rows");
+    if (b->cond_grid && !b->cond_rows && 53 + b->n_hist != u->cond_row_len) return fail(TD_ERR_ARG, "td_sample_grid_batch: 53 + n_hist must equal the model's conditioning row length");
+    std::vector<Buf> hold;
+    NoiseJob nj; CondJob cj; BlendJob bj;
+    int rc;
+    // a failure past this point may leave uploads from the job structs' host arrays in flight: drain the stream before they go
+    auto bail = [&](int code) { (void)hipStreamSynchronize(e->stream); return code; };
+    // host preparation and uploads
+    if ((rc = noise_prepare(e, nj, b->noise_seed, n, b->origins_host, H, W, C, b->tile_h, b->tile_w))) return bail(rc);
+    const void* drows = nullptr;
+    const bool rows_from_grid = u->cond_row_len > 0 && !b->cond_rows;
+    if (rows_from_grid) {
+        if ((rc = cond_prepare(e, cj, b->cond_grid, b->grid_rows, b->grid_cols, n, b->cond_pos_host, b->cond_means_host, b->cond_stds_host, b->hist_host, b->n_hist,
+                               b->noise_level, hold))) return bail(rc);
+        Buf r(new DevBuf());
+        if (r->scratch(e->scratch, (size_t)n * u->cond_row_len * 4) != hipSuccess) return bail(fail(TD_ERR_HIP, "td_sample_grid_batch: scratch allocation"));
+        drows = r->p;
+        hold.push_back(std::move(r));
+    } else if (u->cond_row_len > 0 && (rc = to_device(e, b->cond_rows, (size_t)n * u->cond_row_len * 4, hold, &drows))) return bail(rc);
+    if (b->canvas && (rc = blend_prepare(e, bj, C, b->Hc, b->Wc, b->size, b->n_rows, b->row_starts_host, b->n_cols, b->col_starts_host, n, b->wi_host, b->wj_host))) return bail(rc);
+    float* x = b->windows_out;
+    if (!x) {
+        Buf xb(new DevBuf());
+        if (xb->scratch(e->scratch, (size_t)n * C * H * W * 4) != hipSuccess) return bail(fail(TD_ERR_HIP, "td_sample_grid_batch: scratch allocation"));
+        x = (float*)xb->p;
+        hold.push_back(std::move(xb));
+    }
+    // the GPU work, back to back
+    if ((rc = noise_enqueue(e, nj, n, H, W, C, b->tile_h, b->tile_w, b->noise_scale, x))) return bail(rc);
+    if (rows_from_grid && (rc = cond_enqueue(e, cj, (float*)drows))) return bail(rc);
+    if ((rc = sample_edm_enqueue(u, nullptr, 1.f, n, H, W, b->n_steps, b->sigmas_host, b->sigma_data, (const float*)drows, nullptr, 0, x, hold))) return bail(rc);
+    if (b->canvas && (rc = blend_enqueue(e, bj, b->canvas, C, b->Hc, b->Wc, b->size, b->n_cols, x, b->accumulate))) return bail(rc);
+    return end_call(e, hold, (!b->cond_rows || is_device_ptr(b->cond_rows)) && (!rows_from_grid || is_device_ptr(b->cond_grid)));
 }
 
 // ---- output composition

@@ -502,6 +502,46 @@ __global__ void window_extract_kernel(const float* __restrict__ img, float* __re
     tiles[(size_t)win * C * size * size + i] = img[((size_t)c * Hc + origins[2 * win] + y) * Wc + origins[2 * win + 1] + x];
 }
 
+// ------------------------------------------------------------------------------------------------ conditioning rows
+// sample_diffusion_base.py:11-48 applied to ONE (1,7,4,4) patch per window, for n windows of a (7,R,Cg) conditioning grid at once: row =
+// [ch 0 (16) | ch 1 (16) | climate means of ch 2..5 over cells [1:3,1:3] (4) | ch 6 (16) | histogram (nh) | noise level (1)], every part times its own
+// fp32 factor.  One thread per output element.  Bit for bit what the host path (sampling._process_cond_img) gives for a batch of one: separately rounded
+// subtract / divide / add / multiply (no contraction), the 2x2 mean summed as (a+b)+(c+d), NaN -> nan_fill and +-inf -> +-FLT_MAX after the normalisation.
+struct CondRowsParams {
+    float mean[7], stdv[7];
+    float factor[6];           // per part: channel 0, channel 1, climate means, channel 6, histogram, noise level
+    float nan_fill;            // float(cond_means[0]): a batch of one puts every NaN under the reference's [0:1] fill
+    float noise_entry;         // (noise_level - 0.5f) * (float)sqrt(12.0), before its factor
+    int R, Cg, nh, n;
+};
+
+__global__ void cond_rows_kernel(const float* __restrict__ grid, const int* __restrict__ pos, const float* __restrict__ hist, float* __restrict__ out, CondRowsParams p) {
+#pragma clang fp contract(off)
+    const int L = 53 + p.nh;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= p.n * L) return;
+    const int win = t / L, k = t % L;
+    const int i0 = pos[2 * win], j0 = pos[2 * win + 1];
+    auto cell = [&](int c, int y, int x) {
+        float v = __fdiv_rn(__fsub_rn(grid[((size_t)c * p.R + i0 + y) * p.Cg + j0 + x], p.mean[c]), p.stdv[c]);
+        if (v != v) v = p.nan_fill;
+        else if (v > 3.402823466e+38f) v = 3.402823466e+38f;
+        else if (v < -3.402823466e+38f) v = -3.402823466e+38f;
+        return v;
+    };
+    float r;
+    if (k < 16) r = __fmul_rn(cell(0, k >> 2, k & 3), p.factor[0]);
+    else if (k < 32) r = __fmul_rn(cell(1, (k - 16) >> 2, k & 3), p.factor[1]);
+    else if (k < 36) {
+        const int c = 2 + (k - 32);
+        const float a = cell(c, 1, 1), b = cell(c, 1, 2), cc = cell(c, 2, 1), d = cell(c, 2, 2);
+        r = __fmul_rn(__fdiv_rn(__fadd_rn(__fadd_rn(a, b), __fadd_rn(cc, d)), 4.f), p.factor[2]);
+    } else if (k < 52) r = __fmul_rn(cell(6, (k - 36) >> 2, k & 3), p.factor[3]);
+    else if (k < 52 + p.nh) r = __fmul_rn(hist[k - 52], p.factor[4]);
+    else r = __fmul_rn(p.noise_entry, p.factor[5]);
+    out[t] = r;
+}
+
 // explicit instantiations used by the engine
 template __global__ void attn_kernel<float>(const float*, float*, int, int);
 template __global__ void attn_kernel<__bf16>(const __bf16*, __bf16*, int, int);

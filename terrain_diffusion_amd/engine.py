@@ -27,6 +27,10 @@ class Engine:
         if key == "async":   # the shadow on_stream restores on exit follows the documented C-ABI knob, whoever sets it (round-5 advisor)
             self._async = bool(int(value))
 
+    def get_option(self, key, default):
+        """the value set_option stored for `key`, or `default` when it was never set"""
+        return int(lib().td_engine_get_option(self._h, key.encode(), int(default)))
+
     def synchronize(self):
         check(lib().td_engine_synchronize(self._h))
 

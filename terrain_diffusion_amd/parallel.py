@@ -178,7 +178,7 @@ def engine_fns(model, scheduler, plan, cond_inputs, *, cond_means, cond_stds, no
         for b0 in range(0, len(windows), max_batch):
             chunk = windows[b0:b0 + max_batch]
             origins = [(noise_origin[0] + plan.h_starts[ic], noise_origin[1] + plan.w_starts[jc]) for ic, jc in chunk]
-            c58 = _s._tile_conditioning(cond, chunk, histogram_raw, cond_means, cond_stds, noise_level)
+            c58 = _s.tile_conditioning_rows(model.engine, cond, chunk, histogram_raw, cond_means, cond_stds, noise_level)   # td_cond_rows: one launch
             outs.append(_s.sample_independent_tiles(model, scheduler, origins, c58, steps=steps, tile_size=plan.size, channels=channels,
                                                     noise_seed=noise_seed, return_raw=True))
         return torch.cat(outs)
@@ -269,7 +269,7 @@ def consistency_engine_fns(model, plan, cond_inputs, *, cond_means, cond_stds, n
             chunk = windows[b0:b0 + max_batch]
             origins = [(noise_origin[0] + plan.h_starts[ic], noise_origin[1] + plan.w_starts[jc]) for ic, jc in chunk]
             z = _noise.gaussian_noise_patches(noise_seed + k, origins, plan.size, plan.size, channels=channels, tile_h=64, tile_w=64, device=dev)
-            c58 = _s._tile_conditioning(cond, chunk, histogram_raw, cond_means, cond_stds, noise_level).to(dev).contiguous()
+            c58 = _s.tile_conditioning_rows(model.engine, cond, chunk, histogram_raw, cond_means, cond_stds, noise_level).to(dev).contiguous()
             prev = None if prev_tiles is None else prev_tiles[b0:b0 + max_batch].contiguous()
             out = torch.empty_like(z)
             check(lib().td_sample_consistency(model._h, z.shape[0], plan.size, plan.size, float(t), float(sigma_data), ptr(prev), ptr(z), ptr(c58), ptr(out)))

@@ -12,7 +12,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, GridBatch
 from .engine import ptr
 from . import noise as _noise
 
@@ -132,6 +132,42 @@ def _tile_conditioning(cond_inputs, tiles, histogram_raw, cond_means, cond_stds,
     return torch.as_tensor(cond_inputs, dtype=torch.float32).view(1, -1).expand(len(tiles), -1).contiguous()
 
 
+def _np32(t):
+    return np.ascontiguousarray(torch.as_tensor(t, dtype=torch.float32).detach().cpu().numpy().reshape(-1))
+
+
+def _cond_grid_args(cond_inputs, histogram_raw, cond_means, cond_stds, noise_level):
+    """What td_cond_rows takes besides the window positions, or None when the inputs are not the one-grid case it covers (a (1,7,R,Cg) grid, 7
+    statistics, one histogram row, one noise level): (grid (7,R,Cg) contiguous fp32 on its device, means, stds, hist as float32 arrays, noise level)."""
+    g = torch.as_tensor(cond_inputs)
+    if g.ndim != 4 or g.shape[0] != 1 or g.shape[1] != 7 or g.shape[2] < 4 or g.shape[3] < 4:
+        return None
+    means, stds, hist = _np32(cond_means), _np32(cond_stds), torch.as_tensor(histogram_raw, dtype=torch.float32)
+    nl = torch.as_tensor(noise_level, dtype=torch.float32)
+    if means.size != 7 or stds.size != 7 or hist.numel() != hist.shape[-1] or nl.numel() != 1:
+        return None
+    return g[0].to(torch.float32).contiguous(), means, stds, _np32(hist), float(nl.reshape(()))
+
+
+def cond_rows(engine, cond_inputs, tiles, histogram_raw, cond_means, cond_stds, noise_level=0.0, args=None):
+    """_tile_conditioning on the GPU (td_cond_rows): the (n, 53 + nh) conditioning rows of the windows `tiles` = [(ic, jc), ...] of one (1,7,R,Cg)
+    grid (host or device), bit for bit what _process_cond_img gives window by window, as a device tensor."""
+    g, means, stds, hist, nl = args or _cond_grid_args(cond_inputs, histogram_raw, cond_means, cond_stds, noise_level)
+    pos = np.ascontiguousarray(np.asarray(tiles, dtype=np.int32).reshape(-1, 2))
+    out = torch.empty((len(pos), 53 + hist.size), dtype=torch.float32, device=torch.device("cuda", engine.device_id))
+    check(lib().td_cond_rows(engine._h, ptr(g), g.shape[1], g.shape[2], len(pos), ptr(pos), ptr(means), ptr(stds), ptr(hist), hist.size, nl, ptr(out)))
+    return out
+
+
+def tile_conditioning_rows(engine, cond_inputs, tiles, histogram_raw, cond_means, cond_stds, noise_level):
+    """The conditioning rows of a window batch for the engine-backed samplers: td_cond_rows where it applies (engine option "grid_fused", default 1),
+    the host path (_tile_conditioning) for a 1-D row, other shapes and without an engine."""
+    args = _cond_grid_args(cond_inputs, histogram_raw, cond_means, cond_stds, noise_level) if engine is not None and engine.get_option("grid_fused", 1) != 0 else None
+    if args is None:
+        return _tile_conditioning(torch.as_tensor(cond_inputs, dtype=torch.float32), tiles, histogram_raw, cond_means, cond_stds, noise_level)
+    return cond_rows(engine, cond_inputs, tiles, histogram_raw, cond_means, cond_stds, noise_level, args=args)
+
+
 def blend_windows(engine, canvas, tiles, tile_idx, h_starts, w_starts, size, accumulate=True):
     """canvas (C+1,Hc,Wc) += windows (deterministic gather, reference loop order)."""
     C_, Hc, Wc = canvas.shape[0] - 1, canvas.shape[1], canvas.shape[2]
@@ -218,21 +254,52 @@ def sample_base_diffusion(model, scheduler, shape, cond_inputs, *, cond_means, c
     run = all_tiles if tiles is None else [t for t in all_tiles if t in set(tiles)]
     canvas = torch.zeros((C_ + 1, H, W), dtype=torch.float32, device=dev)
     windows = {}
+    # engine option "grid_fused" (default 1): a window batch is ONE engine call (td_sample_grid_batch: noise, conditioning rows, both sampler lanes and
+    # the blend enqueued back to back, one wait) instead of four calls with the conditioning rows built window by window on the host in between;
+    # autoguidance and conditioning shapes td_cond_rows does not cover stay on the four calls
+    grid_args = _cond_grid_args(cond_inputs, histogram_raw, cond_means, cond_stds, noise_level) if cond_inputs.ndim == 4 else None
+    fused = eng.get_option("grid_fused", 1) != 0 and (guide_model is None or guidance_scale == 1.0) and (cond_inputs.ndim == 1 or grid_args is not None)
+    # initial_noise[..., i0:i1, j0:j1] of one shared field (sample_diffusion_base.py:124,145) == windows of the absolute field
+    # the bounded sampler's noise field is this package's own convention (the reference draws torch.randn here): 64x64 noise tiles,
+    # or one tile size that holds the window when the window is larger
+    nth, ntw = max(64, th), max(64, tw)
+    if fused:
+        sig = np.ascontiguousarray(scheduler.sigmas.to(torch.float32).cpu().numpy())
+        eng.set_option("solver_order", int(getattr(scheduler.config, "solver_order", 2)))
+        eng.set_option("lower_order_final", int(bool(getattr(scheduler.config, "lower_order_final", True))))   # as sample_tiles_edm sets them
+        rs, cs = np.asarray(h_starts, dtype=np.int32), np.asarray(w_starts, dtype=np.int32)
     for b0 in range(0, len(run), max_batch):
         chunk = run[b0:b0 + max_batch]
         origins = [(noise_origin[0] + h_starts[ic], noise_origin[1] + w_starts[jc]) for ic, jc in chunk]
-        # initial_noise[..., i0:i1, j0:j1] of one shared field (sample_diffusion_base.py:124,145) == windows of the absolute field
-        # the bounded sampler's noise field is this package's own convention (the reference draws torch.randn here): 64x64 noise tiles,
-        # or one tile size that holds the window when the window is larger
-        nth, ntw = max(64, th), max(64, tw)
-        x = _noise.gaussian_noise_patches(noise_seed, origins, th, tw, channels=C_, tile_h=nth, tile_w=ntw, scale=sigma0, device=dev)
-        cond = _tile_conditioning(cond_inputs, chunk, histogram_raw, cond_means, cond_stds, noise_level).to(dev).contiguous()
-        sample_tiles_edm(model, scheduler, x, cond, steps, guide_model=guide_model, guidance_scale=guidance_scale)
+        if fused:
+            org = np.ascontiguousarray(np.asarray(origins, dtype=np.int64).reshape(-1, 2))
+            _noise.check_origins(org, th, tw)
+            pos = np.ascontiguousarray(np.asarray(chunk, dtype=np.int32).reshape(-1, 2))
+            wi, wj = np.ascontiguousarray(pos[:, 0]), np.ascontiguousarray(pos[:, 1])
+            x = torch.empty((len(chunk), C_, th, tw), dtype=torch.float32, device=dev) if (return_windows or tile_size is None) else None
+            b = GridBatch(noise_seed=int(noise_seed) & _noise.M64, n=len(chunk), H=th, W=tw, tile_h=nth, tile_w=ntw, noise_scale=sigma0, origins_host=ptr(org),
+                          n_steps=steps, sigma_data=sd, sigmas_host=ptr(sig), windows_out=ptr(x))
+            if grid_args is not None:
+                g, means, stds, hist, nl = grid_args
+                b.cond_grid, b.grid_rows, b.grid_cols, b.cond_pos_host = ptr(g), g.shape[1], g.shape[2], ptr(pos)
+                b.cond_means_host, b.cond_stds_host, b.hist_host, b.n_hist, b.noise_level = ptr(means), ptr(stds), ptr(hist), hist.size, nl
+            else:
+                rows = cond_inputs.view(1, -1).expand(len(chunk), -1).contiguous()
+                b.cond_rows = ptr(rows)
+            if tile_size is not None:
+                b.canvas, b.Hc, b.Wc, b.size, b.accumulate = ptr(canvas), H, W, tile_size, 1
+                b.n_rows, b.row_starts_host, b.n_cols, b.col_starts_host, b.wi_host, b.wj_host = len(rs), ptr(rs), len(cs), ptr(cs), ptr(wi), ptr(wj)
+            check(lib().td_sample_grid_batch(model._h, C.byref(b)))
+        else:
+            x = _noise.gaussian_noise_patches(noise_seed, origins, th, tw, channels=C_, tile_h=nth, tile_w=ntw, scale=sigma0, device=dev)
+            cond = _tile_conditioning(cond_inputs, chunk, histogram_raw, cond_means, cond_stds, noise_level).to(dev).contiguous()
+            sample_tiles_edm(model, scheduler, x, cond, steps, guide_model=guide_model, guidance_scale=guidance_scale)
         if tile_size is None:
             return x
         if return_windows:
             windows.update({t: x[k].clone() for k, t in enumerate(chunk)})
-        blend_windows(eng, canvas, x, chunk, h_starts, w_starts, tile_size, accumulate=True)
+        if not fused:
+            blend_windows(eng, canvas, x, chunk, h_starts, w_starts, tile_size, accumulate=True)
     out = canvas if return_canvas else blend_normalize(eng, canvas, 1.0 / sd)[None]
     return (out, windows) if return_windows else out
 

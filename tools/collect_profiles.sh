@@ -14,7 +14,9 @@ for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum
   timeout -k 10 900 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$tag -- $BENCH > $OUT/pmc_$tag.log 2>&1 || { echo "pmc pass $tag failed: $?"; tail -5 $OUT/pmc_$tag.log; exit 1; }
 done
 B1="python $R/bench.py --workload tiles --tiles-per-step 1 --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-profile --no-latency"
-for c in "FETCH_SIZE" "WRITE_SIZE"; do
+# SKIP_B1=1: a re-stamp of the batch-64 files only (the single-tile path unchanged: batch1_hbm_traffic.json carries no build stamp)
+B1C="FETCH_SIZE WRITE_SIZE"; if [ -n "$SKIP_B1" ]; then B1C=""; fi
+for c in $B1C; do
   timeout -k 10 600 rocprofv3 --pmc $c --output-format csv -d $OUT/b1pmc_$c -- $B1 > $OUT/b1pmc_$c.log 2>&1 || { echo "batch-1 pmc pass $c failed: $?"; tail -5 $OUT/b1pmc_$c.log; exit 1; }
 done
 python3 - <<'PY'
