@@ -6,6 +6,7 @@ by design: all tiles of a phase are batched through the engine (they are indepen
 from the portable absolute-coordinate field (world_pipeline.py:66-115) instead of torch.randn, and the blend is a
 deterministic gather in the reference's loop order.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -18,6 +19,25 @@ from . import noise as _noise
 
 
 from .geometry import tile_starts as _tile_starts  # noqa: E402  (reference name kept as an alias)
+
+
+@contextlib.contextmanager
+def _solver_options(engine, scheduler):
+    """The scheduler's solver order and lower_order_final as engine options for the sampler calls of the body; what the engine held before is put
+    back on exit (one engine per process: a third-order run must not leave every later caller's sampler at order 3).  The samplers read both on
+    the host while they enqueue, so the values may go back as soon as the call has returned, in enqueue-only mode too."""
+    # dpmsolver.py:694-696: the second-to-last step of a third-order run drops to second order only when config.lower_order_final is set (and the
+    # run has < 15 steps); the engine's order schedule follows the scheduler's flag instead of assuming the released default
+    want = {"solver_order": int(getattr(scheduler.config, "solver_order", 2)),
+            "lower_order_final": int(bool(getattr(scheduler.config, "lower_order_final", True)))}
+    before = {"solver_order": engine.get_option("solver_order", 2), "lower_order_final": engine.get_option("lower_order_final", 1)}
+    try:
+        for k, v in want.items():
+            engine.set_option(k, v)
+        yield
+    finally:
+        for k, v in before.items():
+            engine.set_option(k, v)
 
 
 def _linear_weight_window(size, device="cuda", dtype=torch.float32):
@@ -194,18 +214,15 @@ def sample_tiles_edm(model, scheduler, x, cond, steps, cond_img=None, guide_mode
     (coarse stage: world_pipeline.py:946 `torch.cat([scaled_in, cond_img], dim=1)`)."""
     scheduler.set_timesteps(steps)
     sig = scheduler.sigmas.to(torch.float32).cpu().contiguous()
-    model.engine.set_option("solver_order", int(getattr(scheduler.config, "solver_order", 2)))
-    # dpmsolver.py:694-696: the second-to-last step of a third-order run drops to second order only when config.lower_order_final is set (and the
-    # run has < 15 steps); the engine's order schedule follows the scheduler's flag instead of assuming the released default
-    model.engine.set_option("lower_order_final", int(bool(getattr(scheduler.config, "lower_order_final", True))))
     n, _, H, W = x.shape
     cimg = 0 if cond_img is None else cond_img.shape[1]
-    if guide_model is not None and guidance_scale != 1.0:   # autoguidance (sample_diffusion_base.py:105-110)
-        if cond_img is not None:
-            raise NotImplementedError("autoguidance with conditioning-image channels")
-        check(lib().td_sample_edm_guided(model._h, guide_model._h, float(guidance_scale), n, H, W, steps, ptr(sig), float(scheduler.config.sigma_data), ptr(cond), ptr(x)))
-        return x
-    check(lib().td_sample_edm_img(model._h, n, H, W, steps, ptr(sig), float(scheduler.config.sigma_data), ptr(cond), ptr(cond_img), cimg, ptr(x)))
+    with _solver_options(model.engine, scheduler):
+        if guide_model is not None and guidance_scale != 1.0:   # autoguidance (sample_diffusion_base.py:105-110)
+            if cond_img is not None:
+                raise NotImplementedError("autoguidance with conditioning-image channels")
+            check(lib().td_sample_edm_guided(model._h, guide_model._h, float(guidance_scale), n, H, W, steps, ptr(sig), float(scheduler.config.sigma_data), ptr(cond), ptr(x)))
+            return x
+        check(lib().td_sample_edm_img(model._h, n, H, W, steps, ptr(sig), float(scheduler.config.sigma_data), ptr(cond), ptr(cond_img), cimg, ptr(x)))
     return x
 
 
@@ -265,8 +282,6 @@ def sample_base_diffusion(model, scheduler, shape, cond_inputs, *, cond_means, c
     nth, ntw = max(64, th), max(64, tw)
     if fused:
         sig = np.ascontiguousarray(scheduler.sigmas.to(torch.float32).cpu().numpy())
-        eng.set_option("solver_order", int(getattr(scheduler.config, "solver_order", 2)))
-        eng.set_option("lower_order_final", int(bool(getattr(scheduler.config, "lower_order_final", True))))   # as sample_tiles_edm sets them
         rs, cs = np.asarray(h_starts, dtype=np.int32), np.asarray(w_starts, dtype=np.int32)
     for b0 in range(0, len(run), max_batch):
         chunk = run[b0:b0 + max_batch]
@@ -289,7 +304,8 @@ def sample_base_diffusion(model, scheduler, shape, cond_inputs, *, cond_means, c
             if tile_size is not None:
                 b.canvas, b.Hc, b.Wc, b.size, b.accumulate = ptr(canvas), H, W, tile_size, 1
                 b.n_rows, b.row_starts_host, b.n_cols, b.col_starts_host, b.wi_host, b.wj_host = len(rs), ptr(rs), len(cs), ptr(cs), ptr(wi), ptr(wj)
-            check(lib().td_sample_grid_batch(model._h, C.byref(b)))
+            with _solver_options(eng, scheduler):   # as sample_tiles_edm sets them
+                check(lib().td_sample_grid_batch(model._h, C.byref(b)))
         else:
             x = _noise.gaussian_noise_patches(noise_seed, origins, th, tw, channels=C_, tile_h=nth, tile_w=ntw, scale=sigma0, device=dev)
             cond = _tile_conditioning(cond_inputs, chunk, histogram_raw, cond_means, cond_stds, noise_level).to(dev).contiguous()

@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _attn_twin as at
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -140,22 +141,21 @@ def _engine_arm(which, T, n, H, W, mfma):
     m = td.EDMUnet2D(**cfg, dtype=T).load_state_dict(sd)
     stats = []
     try:
-        eng.set_option("attn_mfma", 1 if mfma else 0)
-        m(x.cuda(), torch.full((n,), 1.1), cond)
-        torch.cuda.synchronize()
-        sel = ct.pick_samples(n)
-        for blk in blocks:
-            qkv = m.read_activation(n, H, W, blk + ".attn_qkv")[sel]
-            att = m.read_activation(n, H, W, blk + ".attn")[sel]
-            assert att.shape == (len(sel), qkv.shape[1] // 3) + qkv.shape[2:]
-            tokens, heads = qkv.shape[2] * qkv.shape[3], qkv.shape[1] // 192
-            name = f"engine {which} {T} n{n} {H}x{W} {blk}.attn ({tokens} tokens, {heads} heads, {'MFMA ' + str(dispatch(n, heads, tokens, tokens, 64)) if mfma and T == 'bf16' else 'scalar kernel'})"
-            st = at.check_engine_attention(qkv, att, T, mfma and T == "bf16", name, "cuda")
-            stats.append(st)
-            LINES.append(at.line(st))
-            print(LINES[-1])
+        with pinned(eng, attn_mfma=1 if mfma else 0):
+            m(x.cuda(), torch.full((n,), 1.1), cond)
+            torch.cuda.synchronize()
+            sel = ct.pick_samples(n)
+            for blk in blocks:
+                qkv = m.read_activation(n, H, W, blk + ".attn_qkv")[sel]
+                att = m.read_activation(n, H, W, blk + ".attn")[sel]
+                assert att.shape == (len(sel), qkv.shape[1] // 3) + qkv.shape[2:]
+                tokens, heads = qkv.shape[2] * qkv.shape[3], qkv.shape[1] // 192
+                name = f"engine {which} {T} n{n} {H}x{W} {blk}.attn ({tokens} tokens, {heads} heads, {'MFMA ' + str(dispatch(n, heads, tokens, tokens, 64)) if mfma and T == 'bf16' else 'scalar kernel'})"
+                st = at.check_engine_attention(qkv, att, T, mfma and T == "bf16", name, "cuda")
+                stats.append(st)
+                LINES.append(at.line(st))
+                print(LINES[-1])
     finally:
-        eng.set_option("attn_mfma", 1)
         m.close()
     return stats
 
@@ -196,11 +196,10 @@ def test_scalar_kernel_is_refused_beyond_64_tokens():
     for T, opt in (("bf16", 0), ("fp16", 1), ("fp32", 1)):
         m = td.EDMUnet2D(**cfg, dtype=T).load_state_dict(sd)
         try:
-            eng.set_option("attn_mfma", opt)
-            with pytest.raises(TdError, match="64 tokens"):
-                m(x, torch.full((1,), 0.9), c)
+            with pinned(eng, attn_mfma=opt):
+                with pytest.raises(TdError, match="64 tokens"):
+                    m(x, torch.full((1,), 0.9), c)
         finally:
-            eng.set_option("attn_mfma", 1)
             m.close()
 
 

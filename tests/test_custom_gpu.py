@@ -10,6 +10,7 @@ import torch
 
 import _custom_twin as twin
 import test_custom_cpu as cpu
+from _engine_opts import engine_options_guard  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 F = np.float32

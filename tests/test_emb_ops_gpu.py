@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _emb_twin as et
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -50,9 +51,9 @@ def _call(m, case):
     if kind in ("forward", "uniform"):
         m(x, case["t"] if kind == "forward" else case["t"].expand(n).contiguous(), cond)
     elif kind == "edm":
-        m.engine.set_option("solver_order", 2)
         x = (x * 80.0).contiguous()
-        check(lib().td_sample_edm(m._h, n, H, W, 5, ptr(case["sigmas"].contiguous()), float(case["sigma_data"]), ptr(m.cond_rows(cond, n, "cuda")), ptr(x)))
+        with pinned(m.engine, solver_order=2):
+            check(lib().td_sample_edm(m._h, n, H, W, 5, ptr(case["sigmas"].contiguous()), float(case["sigma_data"]), ptr(m.cond_rows(cond, n, "cuda")), ptr(x)))
     else:
         consistency_step(m, float(case["t"][0]), 0.5, None, x, cond=m.cond_rows(cond, n, "cuda"))
     torch.cuda.synchronize()

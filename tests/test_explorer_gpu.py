@@ -13,6 +13,7 @@ import torch
 
 import _explorer_twin as twin
 import test_explorer_cpu as cpu
+from _engine_opts import engine_options_guard  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 F = np.float32

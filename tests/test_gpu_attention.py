@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import rel_rms
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -122,11 +123,8 @@ def test_unet_attention_blocks_use_the_mfma_kernel_and_match():
     g = torch.Generator(device="cuda").manual_seed(0)
     x, c, t = torch.randn(4, 5, 64, 64, device="cuda", generator=g), torch.randn(4, 58, device="cuda", generator=g), torch.full((4,), 0.9)
     a = m(x, t, [c])
-    try:
-        eng.set_option("attn_mfma", 0)
+    with pinned(eng, attn_mfma=0):
         b = m(x, t, [c])
-    finally:
-        eng.set_option("attn_mfma", 1)
     assert rel_rms(a.cpu().numpy(), b.cpu().numpy()) < 1e-2
     ref = OracleUnet(cfg, sd)(x.cpu(), t, [c.cpu()])
     assert rel_rms(a.cpu().numpy(), ref.detach().numpy()) < 2e-2

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import rel_rms
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,14 +50,13 @@ def test_base_forward_batch64_vs_oracle(td, base):
     eng = get_engine("cuda")
     x, c = _batch_inputs(64)
     t = torch.full((64,), 1.1)
-    eng.set_option("profile", 1)
-    eng.profile_read(reset=True)
-    try:
-        y = m(x.cuda(), t, [c.cuda()])
-        labels = [l for l, _, _ in eng.profile_ops()]
-    finally:
+    with pinned(eng, profile=1):
         eng.profile_read(reset=True)
-        eng.set_option("profile", 0)
+        try:
+            y = m(x.cuda(), t, [c.cuda()])
+            labels = [l for l, _, _ in eng.profile_ops()]
+        finally:
+            eng.profile_read(reset=True)
     assert any(" f2b " in l for l in labels), "the 8-wave big tile variant did not run at batch 64"
     # both cout tilings and both wave counts of the LDS-DMA flavour are exercised at this batch size (which layer gets which is the plan's choice)
     assert any("bn128" in l and " f2" in l for l in labels) and any("bn96" in l and " f2b " in l for l in labels) and any(" f2s " in l for l in labels), labels[:5]
@@ -77,28 +77,19 @@ LAYERS = ["enc.512x512_conv", "enc.512x512_block0.conv_res0", "enc.512x512_block
 
 
 def _forward_with(eng, m, x, t, c, n, **opts):
-    prev = {}
-    try:
-        # the arms of these tests compare tile shapes of the LDS-DMA conv (conv_glds): the small-batch flavour (round 4, conv_sb.hip -- its own tile
-        # hooks are sb_mt / sb_nt, tests/test_gpu_small_batch.py) would otherwise take the small grids of a batch <= 8 whatever the glds_* hooks say
-        # (and the wide tile of round 6, conv_glds_wide.hip -- another K order, compared with a tolerance in test_wide_tile_*  -- would take the 64x64 /
-        # 32x32 levels of a 64-window batch)
-        opts = dict(opts, sb=opts.get("sb", 0), glds_wide=opts.get("glds_wide", 0))
-        for k, v in opts.items():
-            eng.set_option(k, v)
-            prev[k] = {"glds_variant": -1, "glds_bn": 0, "glds_splitk": 1, "glds_dma1x1": 1, "sb": 1, "glds_wide": 1}[k]
-        eng.set_option("profile", 1)
-        eng.profile_read(reset=True)
-        y = m(x, t, [c])
-        labels = [l for l, _, _ in eng.profile_ops()]
-        eng.profile_read(reset=True)
-        eng.set_option("profile", 0)
+    # the arms of these tests compare tile shapes of the LDS-DMA conv (conv_glds): the small-batch flavour (round 4, conv_sb.hip -- its own tile
+    # hooks are sb_mt / sb_nt, tests/test_gpu_small_batch.py) would otherwise take the small grids of a batch <= 8 whatever the glds_* hooks say
+    # (and the wide tile of round 6, conv_glds_wide.hip -- another K order, compared with a tolerance in test_wide_tile_*  -- would take the 64x64 /
+    # 32x32 levels of a 64-window batch)
+    opts = dict(opts, sb=opts.get("sb", 0), glds_wide=opts.get("glds_wide", 0))
+    with pinned(eng, **opts):
+        with pinned(eng, profile=1):
+            eng.profile_read(reset=True)
+            y = m(x, t, [c])
+            labels = [l for l, _, _ in eng.profile_ops()]
+            eng.profile_read(reset=True)
         acts = {l: m.read_activation(n, 64, 64, l, max_elems=n * 384 * 64 * 64) for l in LAYERS}
         return y, acts, labels
-    finally:
-        eng.set_option("profile", 0)
-        for k, v in prev.items():
-            eng.set_option(k, v)
 
 
 @pytest.mark.parametrize("n", [64, 8])
@@ -150,17 +141,16 @@ def test_fewcout_output_conv_against_the_mfma_tile(td, out_channels):
             t = torch.full((n,), 0.9)
             outs, tags = {}, {}
             for v in (0, 1):
-                eng.set_option("fewcout", v)
-                eng.set_option("profile", 1); eng.profile_read(reset=True)
-                outs[v] = m(x, t, []).clone()
-                tags[v] = [l for l, _, _ in eng.profile_ops() if l.startswith("out_conv")]
-                eng.profile_read(reset=True)
+                with pinned(eng, fewcout=v, profile=1):
+                    eng.profile_read(reset=True)
+                    outs[v] = m(x, t, []).clone()
+                    tags[v] = [l for l, _, _ in eng.profile_ops() if l.startswith("out_conv")]
+                    eng.profile_read(reset=True)
             assert len(tags[1]) == 1 and " f6 " in tags[1][0] and " f6 " not in tags[0][0], tags
             e = rel_rms(outs[1].cpu().numpy(), outs[0].cpu().numpy())
             print(f"few-cout output conv {n} x {h} x {w}: vs the MFMA tile rel-RMS {e:.2e}   {tags[1][0]}")
             assert torch.isfinite(outs[1]).all() and float(outs[1].abs().mean()) > 1e-4 and e < 1e-5, e
     finally:
-        eng.set_option("profile", 0); eng.set_option("fewcout", 1)
         m.close()
 
 
@@ -177,15 +167,12 @@ def test_wide_tile_persistent_loop_same_bits(td):
     x = torch.from_numpy(rng.standard_normal(5, (4, DECODER_CONFIG["in_channels"], 256, 256))).cuda()
     t = torch.full((4,), 0.9)
     outs, tags = {}, {}
-    try:
-        for v in (0, 1):
-            eng.set_option("glds_wide_persist", v)
-            eng.set_option("profile", 1); eng.profile_read(reset=True)
+    for v in (0, 1):
+        with pinned(eng, glds_wide_persist=v, profile=1):
+            eng.profile_read(reset=True)
             outs[v] = m(x, t, []).clone()
             tags[v] = [l for l, _, _ in eng.profile_ops()]
             eng.profile_read(reset=True)
-    finally:
-        eng.set_option("profile", 0); eng.set_option("glds_wide_persist", 0)
     n_p = sum(" f2wp " in l for l in tags[1])
     print("launches on the persistent loop:", n_p, "of", sum(" f2w" in l for l in tags[1]), "wide launches")
     assert n_p >= 4 and all(" f2wp " not in l for l in tags[0]), (n_p, tags[1])
@@ -213,16 +200,12 @@ def test_wide_tile_against_the_other_tiles_and_the_oracle(td, base, n, hw):
         if hw == 64:
             res[k] = _forward_with(eng, m, x, t, c, n, **o)
         else:
-            try:
-                for kk, v in o.items():
-                    eng.set_option(kk, v)
-                eng.set_option("profile", 1); eng.profile_read(reset=True)
+            with pinned(eng, **o, profile=1):
+                eng.profile_read(reset=True)
                 y = m(x, t, [c])
                 labels = [l for l, _, _ in eng.profile_ops()]
                 eng.profile_read(reset=True)
                 res[k] = (y, {}, labels)
-            finally:
-                eng.set_option("profile", 0); eng.set_option("glds_wide", 1); eng.set_option("sb", 1)
     n_w = {k: sum(" f2w " in l for l in res[k][2]) for k in res}
     print("launches on the wide tile:", n_w)
     assert n_w["off"] == 0 and n_w["force"] > n_w["auto"] and (n_w["auto"] >= 10 if (n, hw) == (64, 64) else True), n_w
@@ -258,16 +241,13 @@ def test_conv_1x1_dma_ragged_tiles_bit_identical_and_vs_oracle(td, base, n, hw, 
     c = torch.from_numpy(rng.standard_normal(32, (n, 58))).cuda()
     t = torch.full((n,), 0.9)
     ys = {}
-    try:
-        for o in (0, 1):
-            eng.set_option("glds_splitk", splitk); eng.set_option("glds_dma1x1", o); eng.set_option("sb", 0)   # conv_glds' own split-K + 1x1 paths
-            eng.set_option("profile", 1); eng.profile_read(reset=True)
+    for o in (0, 1):
+        with pinned(eng, glds_splitk=splitk, glds_dma1x1=o, sb=0, profile=1):   # conv_glds' own split-K + 1x1 paths
+            eng.profile_read(reset=True)
             ys[o] = m(x, t, [c]).clone()
             labels = [l for l, _, _ in eng.profile_ops()]
-            eng.profile_read(reset=True); eng.set_option("profile", 0)
-            assert any(" f2" in l and "conv_res1" in l and l.startswith("dec.") for l in labels), labels[:5]
-    finally:
-        eng.set_option("glds_splitk", 1); eng.set_option("glds_dma1x1", 1); eng.set_option("profile", 0); eng.set_option("sb", 1)
+            eng.profile_read(reset=True)
+        assert any(" f2" in l and "conv_res1" in l and l.startswith("dec.") for l in labels), labels[:5]
     assert torch.equal(ys[0], ys[1]), float((ys[0] - ys[1]).abs().max())
     with torch.no_grad():
         ref = om(x[:1].cpu(), t[:1], [c[:1].cpu()])
@@ -339,8 +319,7 @@ def test_config3_grid32_full_size_one_gpu(td, base):
     from terrain_diffusion_amd.parallel import ShardPlan, engine_fns, blend_region
     m, om = base
     eng = get_engine("cuda")
-    eng.set_option("batch_invariant", 1)
-    try:
+    with pinned(eng, batch_invariant=1):
         sch = td.EDMDPMSolverMultistepScheduler(sigma_min=0.002, sigma_max=80.0, sigma_data=0.5)
         H = W = 1056
         starts = tiling.tile_starts(H, 64, 32)
@@ -376,8 +355,6 @@ def test_config3_grid32_full_size_one_gpu(td, base):
             full[:, y0:y1, x0:x1] = blend_region(plan, r, have, fns[1], fns[2], 5, 1.0 / 0.5)
         assert seam == 32, seam                      # one column (or row) of 32 windows reaches into the neighbour's region
         assert torch.equal(full[None], y), "two-rank canvas differs from the one-rank canvas"
-    finally:
-        eng.set_option("batch_invariant", 0)
 
 
 @pytest.mark.parametrize("dual", [0, 1])
@@ -392,9 +369,7 @@ def test_config3_default_plan_bit_identical_across_rank_counts(td, base, dual):
     from terrain_diffusion_amd.parallel import ShardPlan, engine_fns, blend_region
     m, om = base
     eng = get_engine("cuda")
-    eng.set_option("batch_invariant", 0)
-    eng.set_option("dual_stream", dual)
-    try:
+    with pinned(eng, batch_invariant=0, dual_stream=dual):
         sch = td.EDMDPMSolverMultistepScheduler(sigma_min=0.002, sigma_max=80.0, sigma_data=0.5)
         H = W = 1056
         cond = tiling.synthetic_cond_grid(32, 32)
@@ -416,8 +391,6 @@ def test_config3_default_plan_bit_identical_across_rank_counts(td, base, dual):
             print(f"configs[3] default plan (dual_stream={dual}): {world}-rank canvas vs one-rank canvas: {nbad} differing values")
             assert nbad == 0, f"{world}-rank canvas differs from the one-rank canvas in {nbad} values (default plan, dual_stream={dual})"
             del tiles, full
-    finally:
-        eng.set_option("dual_stream", 0)
 
 
 def test_fp16_tile_variants_bit_identical_and_close_to_bf16(td):
@@ -537,12 +510,13 @@ def test_decoder_window_at_real_size(td, dtype, tol):
     ds = build_decoder_stage(md, src, seed=1234, tile_size=512, tile_stride=384)
     from terrain_diffusion_amd.engine import get_engine
     eng = get_engine("cuda")
-    eng.set_option("profile", 1); eng.profile_read(reset=True)
-    try:
-        out = ds.f([(0, 1, -2)], [lat_win])[0]
-        labels = [l for l, _, _ in eng.profile_ops()]
-    finally:
-        eng.profile_read(reset=True); eng.set_option("profile", 0)
+    with pinned(eng, profile=1):
+        eng.profile_read(reset=True)
+        try:
+            out = ds.f([(0, 1, -2)], [lat_win])[0]
+            labels = [l for l, _, _ in eng.profile_ops()]
+        finally:
+            eng.profile_read(reset=True)
     if dtype != "fp32":
         # round 6: the 64-cout levels of the decoder run on the wide tile of the LDS-DMA conv, 1x1 tails (the dec blocks' fused skip conv) included --
         # the LDS-DMA-streamed tail of conv_glds_wide.hip is what this window exercises against the oracle

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import rel_rms
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -186,13 +187,10 @@ def test_producer_side_activation_is_bit_identical(td):
     t = torch.linspace(-0.5, 1.5, 12)
     for dtype in ("bf16", "fp32"):
         m = td.EDMUnet2D(**cfg, dtype=dtype).load_state_dict(sd)
-        try:
-            eng.set_option("producer_act", 1)
+        with pinned(eng, producer_act=1):
             a = m(x, t, [c])
-            eng.set_option("producer_act", 0)
+        with pinned(eng, producer_act=0):
             b = m(x, t, [c])
-        finally:
-            eng.set_option("producer_act", 1)
         assert torch.equal(a, b), dtype
         m.close()
 
@@ -263,9 +261,10 @@ def test_unknown_engine_option_is_refused(td):
     from terrain_diffusion_amd._lib import lib
     eng = get_engine("cuda")
     with pytest.raises(RuntimeError, match="unknown engine option"):
-        eng.set_option("batch_invarient", 1)
+        eng.set_option("batch_invarient", 1)            # (the one bare call of the suite: the refusal is what is tested, and nothing is stored)
     assert b"batch_invarient" in lib().td_last_error()
-    eng.set_option("batch_invariant", 0)                # the real key is still accepted
+    with pinned(eng, batch_invariant=0):                # the real key is still accepted
+        assert eng.get_option("batch_invariant", -1) == 0
 
 
 def test_on_stream_is_reentrant_and_ordered_behind_the_previous_stream(td):
@@ -344,12 +343,9 @@ def test_solver_step_fused_into_output_conv_is_bit_identical(td, dtype):
     cond = tiling.synthetic_cond_grid(4, 2)
     kw = dict(cond_means=torch.zeros(7), cond_stds=torch.ones(7), noise_level=torch.tensor(0.0), histogram_raw=torch.zeros(1, 5), steps=12, tile_size=16, noise_seed=3)
     outs = {}
-    try:
-        for f in (1, 0):
-            eng.set_option("fuse_solver", f)
+    for f in (1, 0):
+        with pinned(eng, fuse_solver=f):
             outs[f] = td.sample_base_diffusion(m, sch, (1, 5, 40, 24), cond, **kw).clone()
-    finally:
-        eng.set_option("fuse_solver", 1)
     assert torch.isfinite(outs[1]).all() and torch.equal(outs[1], outs[0])
     m.close()
 
@@ -370,20 +366,16 @@ def test_third_order_solver_on_engine(td):
     sch = td.EDMDPMSolverMultistepScheduler(solver_order=3)
     cond = tiling.synthetic_cond_grid(3, 3)
     kw = dict(cond_means=torch.zeros(7), cond_stds=torch.ones(7), noise_level=torch.tensor(0.0), histogram_raw=torch.zeros(1, 5), tile_size=16, noise_seed=11)
-    try:
-        for steps in (6, 16):
-            got = td.sample_base_diffusion(m, sch, (1, 5, 32, 32), cond, steps=steps, **kw).clone()
-            ref = tiling.sample_base_diffusion_tiled(om, (1, 5, 32, 32), cond, steps=steps, tile_size=16, noise_seed=11, solver_order=3)
-            err = rel_rms(got.cpu().numpy(), ref.numpy())
-            print(f"third-order DPM-Solver++, {steps} steps, fp32 engine vs oracle: {err:.2e}")
-            assert err < 1e-5
-            eng.set_option("fuse_solver", 0)
+    for steps in (6, 16):
+        got = td.sample_base_diffusion(m, sch, (1, 5, 32, 32), cond, steps=steps, **kw).clone()
+        ref = tiling.sample_base_diffusion_tiled(om, (1, 5, 32, 32), cond, steps=steps, tile_size=16, noise_seed=11, solver_order=3)
+        err = rel_rms(got.cpu().numpy(), ref.numpy())
+        print(f"third-order DPM-Solver++, {steps} steps, fp32 engine vs oracle: {err:.2e}")
+        assert err < 1e-5
+        assert eng.get_option("solver_order", 2) == 2             # the sampler put back what it found: the scheduler's order is the call's, not the engine's
+        with pinned(eng, fuse_solver=0):
             unfused = td.sample_base_diffusion(m, sch, (1, 5, 32, 32), cond, steps=steps, **kw)
-            eng.set_option("fuse_solver", 1)
-            assert torch.equal(got, unfused)
-        second = td.sample_base_diffusion(m, td.EDMDPMSolverMultistepScheduler(solver_order=2), (1, 5, 32, 32), cond, steps=16, **kw)
-        assert not torch.equal(second, got)                       # the order really changed the trajectory
-    finally:
-        eng.set_option("fuse_solver", 1)
-        eng.set_option("solver_order", 2)
+        assert torch.equal(got, unfused)
+    second = td.sample_base_diffusion(m, td.EDMDPMSolverMultistepScheduler(solver_order=2), (1, 5, 32, 32), cond, steps=16, **kw)
+    assert not torch.equal(second, got)                       # the order really changed the trajectory
     m.close()

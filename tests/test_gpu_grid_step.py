@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
+
 pytestmark = pytest.mark.gpu
 
 MEANS = torch.tensor([0.31, -0.27, 1.9, -0.6, 0.05, 2.4, -1.1])
@@ -78,20 +80,12 @@ def _both_arms(td, eng, model, cond, shape=(1, 5, 48, 48), options=None, **kw):
     """sample_base_diffusion with grid_fused = 1 and = 0 under `options`; every option goes back to what it was"""
     sch = td.EDMDPMSolverMultistepScheduler()
     stats = dict(cond_means=MEANS, cond_stds=STDS, noise_level=torch.tensor(NOISE_LEVEL), histogram_raw=HIST)
-    options = dict(options or {})
-    defaults = {"grid_fused": 1, "dual_stream_min_batch": 32}
-    before = {k: eng.get_option(k, defaults[k]) for k in list(options) + ["grid_fused"]}
     outs = []
-    try:
-        for k, v in options.items():
-            eng.set_option(k, v)
+    with pinned(eng, **(options or {})):
         for fused in (1, 0):
-            eng.set_option("grid_fused", fused)
-            outs.append(td.sample_base_diffusion(model, sch, shape, cond, steps=3, return_windows=kw.get("tile_size", 32) is not None,
-                                                 **{"tile_size": 32, **stats, **kw}))
-    finally:
-        for k, v in before.items():
-            eng.set_option(k, v)
+            with pinned(eng, grid_fused=fused):
+                outs.append(td.sample_base_diffusion(model, sch, shape, cond, steps=3, return_windows=kw.get("tile_size", 32) is not None,
+                                                     **{"tile_size": 32, **stats, **kw}))
     return outs
 
 
@@ -131,7 +125,16 @@ def test_fused_tile_subset(td, eng, model):
 
 
 def test_fused_two_lanes(td, eng, model):
-    a, b = _both_arms(td, eng, model, _grid(), options={"dual_stream_min_batch": 2})
+    """the two-lane branch of td_sample_grid_batch (dual_stream = 1 and a batch of at least dual_stream_min_batch windows) against the four calls, which split
+    the same way in td_sample_edm_img: both options are pinned here, whatever the engine ships with, and the batch is checked to reach the threshold"""
+    with pinned(eng, dual_stream=1, dual_stream_min_batch=2):
+        from terrain_diffusion_amd.geometry import tile_starts
+        n_windows = len(tile_starts(48, 32, 16)) ** 2                  # one batch (max_batch = 64) of the 48 x 48 canvas' windows
+        assert eng.get_option("dual_stream", -1) == 1 and eng.get_option("dual_stream_min_batch", -1) == 2 and n_windows == 4 >= 2
+        assert n_windows >= max(2, eng.get_option("dual_stream_min_batch", -1))      # the engine's own condition for two lanes
+        a, b = _both_arms(td, eng, model, _grid())
+        assert eng.get_option("dual_stream", -1) == 1 and eng.get_option("dual_stream_min_batch", -1) == 2    # (still, after both arms)
+    assert len(a[1]) == len(b[1]) == n_windows                     # lanes of 2 and 2 windows
     _assert_same(a, b)
 
 
@@ -150,14 +153,10 @@ def test_old_exports_match_what_the_fused_call_used(td, eng, model):
     from terrain_diffusion_amd.sampling import blend_windows
     sch = td.EDMDPMSolverMultistepScheduler()
     sch.set_timesteps(3)
-    before = eng.get_option("sampler_stop_after", -1)
-    try:
-        eng.set_option("sampler_stop_after", 0)
+    with pinned(eng, sampler_stop_after=0):
         canvas, wins = td.sample_base_diffusion(model, sch, (1, 5, 48, 48), _grid(), steps=3, tile_size=32, max_batch=3, noise_origin=(-40, 12296),
                                                 return_canvas=True, return_windows=True, cond_means=MEANS, cond_stds=STDS,
                                                 noise_level=torch.tensor(NOISE_LEVEL), histogram_raw=HIST)
-    finally:
-        eng.set_option("sampler_stop_after", before)
     tiles = [(0, 0), (0, 1), (1, 0), (1, 1)]
     starts = [0, 16]
     x = _noise.gaussian_noise_patches(42 + 5819, [(-40 + starts[i], 12296 + starts[j]) for i, j in tiles], 32, 32, channels=5, tile_h=64, tile_w=64,

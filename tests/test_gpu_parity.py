@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import rel_rms
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -186,15 +187,12 @@ def test_tiled_sampler_tiny(td, orc, golden, dtype, tol):
         assert e_b < {"fp32": 1e-5, "bf16": 1e-2, "fp16": 2e-3}[dtype], (key, "chunked vs single batch", e_b)
     from terrain_diffusion_amd.engine import get_engine
     eng = get_engine("cuda")
-    try:
-        eng.set_option("batch_invariant", 1)
+    with pinned(eng, batch_invariant=1):
         ya = _sample(td, m, 32, 32, 6, 16, 42 + 5819)
         yb = _sample(td, m, 32, 32, 6, 16, 42 + 5819, max_batch=2)
         assert torch.equal(ya, yb), ("batch_invariant mode", float((ya - yb).abs().max()))
         e_inv = rel_rms(ya.cpu().numpy(), g["tiny_grid3_steps6"])
         assert e_inv < tol, ("batch_invariant mode vs reference", e_inv)
-    finally:
-        eng.set_option("batch_invariant", 0)
     m.close()
 
 
@@ -305,9 +303,8 @@ def test_unet_glds_flavour_forced(td, orc, golden):
     g = golden("unet")
     eng = get_engine("cuda")
     outs = {}
-    try:
-        for flavour, min_wgs in (("tap", 1 << 30), ("glds", 0)):
-            eng.set_option("glds_min_wgs", min_wgs)
+    for flavour, min_wgs in (("tap", 1 << 30), ("glds", 0)):
+        with pinned(eng, glds_min_wgs=min_wgs):
             cfg = orc["unet"].tiny_config(64, 1)
             m = _model(td, orc, cfg, 77, "bf16")
             x = torch.from_numpy(orc["rng"].standard_normal(7, (2, 5, 16, 16))).cuda()
@@ -322,8 +319,6 @@ def test_unet_glds_flavour_forced(td, orc, golden):
             y2 = m2(x2, torch.tensor([0.9, 0.9, 0.9]), [c2])
             outs[flavour + "2"] = y2.cpu().numpy()
             m2.close()
-    finally:
-        eng.set_option("glds_min_wgs", 192)
     assert rel_rms(outs["glds"], outs["tap"]) < 1e-2
     assert rel_rms(outs["glds2"], outs["tap2"]) < 1e-2
     o2 = orc["unet"].OracleUnet(orc["unet"].tiny_config(64, 2, attn_resolutions=[128]), orc["unet"].synth_state_dict(orc["unet"].tiny_config(64, 2, attn_resolutions=[128]), seed=78))
@@ -367,8 +362,7 @@ def test_sharded_sampling_simulated_ranks(td, orc):
     from terrain_diffusion_amd.parallel import ShardPlan, engine_fns, blend_region
     from oracle import tiling
     eng = get_engine("cuda")
-    eng.set_option("batch_invariant", 1)
-    try:
+    with pinned(eng, batch_invariant=1):
         cfg = orc["unet"].tiny_config(64, 1)
         m = _model(td, orc, cfg, 77, "bf16")
         sch = td.EDMDPMSolverMultistepScheduler()
@@ -378,26 +372,21 @@ def test_sharded_sampling_simulated_ranks(td, orc):
         ref = td.sample_base_diffusion(m, sch, (1, 5, H, W), cond, steps=steps, tile_size=S, noise_seed=7, **kw)
         # the sharded runs also use the two-lane sampler (engine option dual_stream: half-batches on two HIP streams, what bench.py switches on
         # for the strong-scaling workload): in batch-invariant mode the lane split must not change a bit either
-        eng.set_option("dual_stream", 1)
-        eng.set_option("dual_stream_min_batch", 2)
-        for world in (2, 4):
-            plan = ShardPlan(H, W, S, world)
-            fns = engine_fns(m, sch, plan, cond, steps=steps, channels=5, noise_seed=7, noise_origin=(0, 0), max_batch=64, **kw)
-            tiles = [fns[0](plan.windows[r]) for r in range(world)]
-            full = torch.empty((5, H, W), device="cuda")
-            for r in range(world):
-                have = {}
-                for w_ in plan.needed[r]:
-                    o = plan.owner[w_]
-                    have[w_] = tiles[o][plan.windows[o].index(w_)]
-                y0, y1, x0, x1 = plan.regions[r]
-                full[:, y0:y1, x0:x1] = blend_region(plan, r, have, fns[1], fns[2], 5, 1.0 / 0.5)
-            assert torch.equal(full[None], ref), world
+        with pinned(eng, dual_stream=1, dual_stream_min_batch=2):
+            for world in (2, 4):
+                plan = ShardPlan(H, W, S, world)
+                fns = engine_fns(m, sch, plan, cond, steps=steps, channels=5, noise_seed=7, noise_origin=(0, 0), max_batch=64, **kw)
+                tiles = [fns[0](plan.windows[r]) for r in range(world)]
+                full = torch.empty((5, H, W), device="cuda")
+                for r in range(world):
+                    have = {}
+                    for w_ in plan.needed[r]:
+                        o = plan.owner[w_]
+                        have[w_] = tiles[o][plan.windows[o].index(w_)]
+                    y0, y1, x0, x1 = plan.regions[r]
+                    full[:, y0:y1, x0:x1] = blend_region(plan, r, have, fns[1], fns[2], 5, 1.0 / 0.5)
+                assert torch.equal(full[None], ref), world
         m.close()
-    finally:
-        eng.set_option("batch_invariant", 0)
-        eng.set_option("dual_stream", 0)
-        eng.set_option("dual_stream_min_batch", 32)
 
 
 def test_infinite_latent_stage_vs_oracle(td, orc):
@@ -693,14 +682,11 @@ def test_device_resident_cascade_matches_host_resident(td, orc, monkeypatch):
     got2 = graph(True, small)[0][:, 4:44, 2:42]
     assert small.evictions > 0
     assert rel_rms(got2.cpu().numpy(), got.cpu().numpy()) < 1e-5
-    try:
-        eng.set_option("batch_invariant", 1)
+    with pinned(eng, batch_invariant=1):
         ref_inv = graph(True, DeviceTileStore())[0][:, 4:44, 2:42]
         small = DeviceTileStore(cache_size_bytes=3 * 2 * 64 * 64 * 4)
         got_inv = graph(True, small)[0][:, 4:44, 2:42]
         assert small.evictions > 0 and torch.equal(got_inv, ref_inv)
-    finally:
-        eng.set_option("batch_invariant", 0)
     for m_ in (mc, mb, md):
         m_.close()
 
@@ -816,8 +802,7 @@ def test_sharded_two_phase_consistency_on_engine(td, orc):
     from terrain_diffusion_amd.parallel import ShardPlan, consistency_engine_fns, blend_region, sample_base_consistency_sharded
     from oracle import tiling
     eng = get_engine("cuda")
-    eng.set_option("batch_invariant", 1)
-    try:
+    with pinned(eng, batch_invariant=1):
         cfg = orc["unet"].tiny_config(64, 1)
         m = _model(td, orc, cfg, 77, "bf16")
         sch = td.EDMDPMSolverMultistepScheduler()
@@ -849,5 +834,3 @@ def test_sharded_two_phase_consistency_on_engine(td, orc):
                                                for ic, jc in own.windows[r]]).contiguous()
             assert torch.equal(full[None], ref), world
         m.close()
-    finally:
-        eng.set_option("batch_invariant", 0)

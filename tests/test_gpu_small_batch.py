@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import rel_rms
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,12 +42,13 @@ def _inputs(orc, n):
 def _flavours(eng, model, args):
     """flavour tag ('f4m2n2', 'f2s', ...) of every conv launch of one forward, from the engine's profile labels"""
     import re
-    eng.set_option("profile", 1); eng.profile_read(reset=True)
-    try:
-        model(*args)
-        rows = eng.profile_ops()
-    finally:
-        eng.set_option("profile", 0); eng.profile_read(reset=True)
+    with pinned(eng, profile=1):
+        eng.profile_read(reset=True)
+        try:
+            model(*args)
+            rows = eng.profile_ops()
+        finally:
+            eng.profile_read(reset=True)
     return {r[0].split(" [")[0]: re.search(r" (f\d\w*) bn", r[0]).group(1) for r in rows if " [" in r[0]}
 
 
@@ -65,12 +67,9 @@ def test_single_tile_forward_runs_on_the_small_batch_flavour_and_matches_the_ref
     assert err < tol
     assert n4 >= 70, fl   # every conv that used to split K over workgroups (78 of 79 at batch 1)
     assert n5 >= 15, fl   # round 5: the 16x16 level (19 convs) no longer splits K over workgroups (at 8x8 that stays the faster plan: 48 workgroups of 16 couts lose)
-    try:   # the same forward with the flavour switched off: conv_glds + split-K, same bound, and the two agree to bf16 rounding
-        eng.set_option("sb", 0)
+    with pinned(eng, sb=0):   # the same forward with the flavour switched off: conv_glds + split-K, same bound, and the two agree to bf16 rounding
         y0 = m(*args)
         assert not any(v.startswith(("f4", "f5")) for v in _flavours(eng, m, args).values())
-    finally:
-        eng.set_option("sb", 1)
     assert rel_rms(y0.cpu().numpy(), golden("unet")["base_out"]) < tol
     assert rel_rms(y.cpu().numpy(), y0.cpu().numpy()) < tol
 
@@ -82,12 +81,9 @@ def test_every_tile_shape_of_the_small_batch_flavour(td, orc, golden, base, mt, 
     from terrain_diffusion_amd.engine import get_engine
     eng = get_engine("cuda")
     args = _inputs(orc, 1)
-    try:
-        eng.set_option("sb_mt", mt); eng.set_option("sb_nt", nt)
+    with pinned(eng, sb_mt=mt, sb_nt=nt):
         y = base["bf16"](*args)
         fl = _flavours(eng, base["bf16"], args)
-    finally:
-        eng.set_option("sb_mt", 0); eng.set_option("sb_nt", 0)
     tag = f"f4m{mt}n{nt}"
     # (the 128-pixel tile of round 5 exists on 16-wide maps only: the 8x8 level keeps the planner's tile there)
     assert sum(v == tag for v in fl.values()) >= (50 if mt == 4 else 70), fl
@@ -99,12 +95,13 @@ def test_every_tile_shape_of_the_small_batch_flavour(td, orc, golden, base, mt, 
 def _split_k_launches(eng, model, args):
     """conv launches of one forward that split K over workgroups (ks > 1 in the profile label: each has a reduce launch behind it)"""
     import re
-    eng.set_option("profile", 1); eng.profile_read(reset=True)
-    try:
-        model(*args)
-        rows = eng.profile_ops()
-    finally:
-        eng.set_option("profile", 0); eng.profile_read(reset=True)
+    with pinned(eng, profile=1):
+        eng.profile_read(reset=True)
+        try:
+            model(*args)
+            rows = eng.profile_ops()
+        finally:
+            eng.profile_read(reset=True)
     return [r[0] for r in rows if (m_ := re.search(r" ks(\d+) ", r[0])) and int(m_.group(1)) > 1]
 
 
@@ -122,23 +119,17 @@ def test_deep_level_flavour_everywhere_and_no_reduce_launch_in_a_single_tile_for
     sk = _split_k_launches(eng, m, args)
     # (the two 384-cout convs of the 16x16 level's down block give 96 workgroups of 16 couts: below "s16_min_wgs", they keep their split-K plan too)
     assert 0 < len(sk) <= 26 and all("8x8" in l or "128x128_down" in l for l in sk), sk
-    try:
-        eng.set_option("s16", 2)
+    with pinned(eng, s16=2):
         y = m(*args)
         fl = _flavours(eng, m, args)
-    finally:
-        eng.set_option("s16", 1)
     assert sum(v == "f5c16" for v in fl.values()) >= 70, fl
     err = rel_rms(y.cpu().numpy(), golden("unet")["base_out"])
     print(f"s16 everywhere, {dtype}: rel-RMS vs reference {err:.3e}")
     assert err < tol
-    try:
-        eng.set_option("s16", 0)
+    with pinned(eng, s16=0):
         y0 = m(*args)
         assert not any(v.startswith("f5") for v in _flavours(eng, m, args).values())
         assert len(_split_k_launches(eng, m, args)) >= 40
-    finally:
-        eng.set_option("s16", 1)
     assert rel_rms(y0.cpu().numpy(), golden("unet")["base_out"]) < tol
 
 
@@ -164,18 +155,12 @@ def test_ragged_map_and_workgroup_order(td, orc):
     x = torch.from_numpy(orc["rng"].standard_normal(17, (2, cfg["in_channels"], 72, 72))).cuda()
     c = torch.from_numpy(orc["rng"].standard_normal(18, (2, n_cond))).cuda()
     t = torch.full((2,), 0.9)
-    try:
-        eng.set_option("glds", 0); eng.set_option("splitk", 0)
+    with pinned(eng, glds=0, splitk=0):
         ref = m(x, t, [c])
-    finally:
-        eng.set_option("glds", 1); eng.set_option("splitk", 1)
     for order, s16 in ((0, 1), (1, 1), (0, 2), (1, 2)):   # s16 = 2: the 64 px x 16 cout flavour on every eligible layer (ragged 36 / 18 / 9-wide maps)
-        try:
-            eng.set_option("sb_order", order); eng.set_option("s16", s16)
+        with pinned(eng, sb_order=order, s16=s16):   # (on exit: back to the planner's choice)
             y = m(x, t, [c])
             fl = _flavours(eng, m, (x, t, [c]))
-        finally:
-            eng.set_option("sb_order", -1); eng.set_option("s16", 1)   # back to the planner's choice
         assert any(v.startswith("f4" if s16 == 1 else "f5") for v in fl.values()), fl
         e = rel_rms(y.cpu().numpy(), ref.cpu().numpy())
         print(f"ragged 72x72, sb_order {order}, s16 {s16}: rel-RMS vs the per-tap flavour {e:.3e}")

@@ -10,6 +10,7 @@ import torch
 
 import _mc_twin as twin
 from test_mc_cpu import cases, check_case
+from _engine_opts import engine_options_guard  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 F = np.float32

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import _relief_twin as twin
+from _engine_opts import engine_options_guard  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 

@@ -18,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _sampler_twin as tw
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,23 +56,6 @@ def zoo(td):
         m.close()
 
 
-# The engine is one per process and its options outlive a test: older files of the suite leave "glds_min_wgs" = 192 and "dual_stream" = 0 behind (the defaults of earlier
-# rounds; the engine's are 8 and 1), under which the planner picks other flavours for the arms below.  Everything this file depends on is set to the engine's default here.
-ENGINE_DEFAULTS = dict(sb=1, glds=1, glds_wide=1, glds_splitk=1, splitk=1, sb_mt=0, sb_nt=0, s16=1, fewcout=1, glds_min_wgs=8, batch_invariant=0, dual_stream=1,
-                       dual_stream_min_batch=32, graph=1, profile=0, fuse_solver=1, solver_order=2, lower_order_final=1, sampler_stop_after=-1)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def engine_defaults(td):
-    from terrain_diffusion_amd.engine import get_engine
-    eng = get_engine("cuda")
-    for k, v in ENGINE_DEFAULTS.items():
-        eng.set_option(k, v)
-    yield
-    for k, v in ENGINE_DEFAULTS.items():
-        eng.set_option(k, v)
-
-
 class Run:
     """one sampler case on the engine: run(k) = the state after k steps, as tests/_sampler_twin.py's check_trajectory takes it"""
 
@@ -99,16 +83,12 @@ class Run:
         cond = self.cond[sl].contiguous() if self.cond is not None else None
         img = self.img[sl].contiguous().cuda() if self.img is not None else None
         n = x.shape[0]
-        e.set_option("solver_order", self.order); e.set_option("lower_order_final", self.lof); e.set_option("fuse_solver", fuse)
-        e.set_option("sampler_stop_after", -1 if k is None else k)
-        try:
+        with pinned(e, solver_order=self.order, lower_order_final=self.lof, fuse_solver=fuse, sampler_stop_after=-1 if k is None else k):
             if self.guide is not None:
                 check(lib().td_sample_edm_guided(self.m._h, self.guide._h, float(self.gscale), n, self.H, self.W, self.n_steps, ptr(self.sig), SD, ptr(cond), ptr(x)))
             else:
                 check(lib().td_sample_edm_img(self.m._h, n, self.H, self.W, self.n_steps, ptr(self.sig), SD, ptr(cond), ptr(img), self.Cin - self.C, ptr(x)))
             torch.cuda.synchronize()
-        finally:
-            e.set_option("sampler_stop_after", -1); e.set_option("fuse_solver", 1); e.set_option("solver_order", 2); e.set_option("lower_order_final", 1)
         return x.cpu()
 
     def read(self, label, m=None):
@@ -212,7 +192,6 @@ def test_consistency_sampler_elementwise(zoo, which, T, with_sample, t):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the fused epilogue
-DEFAULTS = dict(sb=1, glds=1, glds_splitk=1, sb_mt=0, sb_nt=0, s16=1, fewcout=1)
 ANY = ("f0", "f2", "f4", "f5")     # the planner's choice for the 5-cout output conv under the arm's options: recorded, and judged over all arms by the closing test
 # name -> (model, T, n, H, W, engine options (as in test_conv_ops_gpu.ARMS), flavour families the fused out_conv may be carried by)
 FUSED = {
@@ -228,6 +207,9 @@ FUSED = {
     "base bf16 n2 per-tap kernel": ("base", "bf16", 2, 64, 64, dict(glds=0), ("f0",)),
     "base bf16 n1 per-tap kernel": ("base", "bf16", 1, 64, 64, dict(glds=0), ("f0",)),
     "base bf16 n8 default plan": ("base", "bf16", 8, 64, 64, {}, ANY),
+    # the plan that ships: with dual_stream = 1 a 64-window batch of the grid sampler runs as two lanes of N = 32, each on this plan.  A 32-row call of its own
+    # would itself split into two lanes of 16 (dual_stream_min_batch = 32), so the arm runs single-lane: one lane of the shipped 64-window call, on its own.
+    "base bf16 n32 default plan": ("base", "bf16", 32, 64, 64, dict(dual_stream=0), ANY),
     "base bf16 n3 56x88": ("base", "bf16", 3, 56, 88, {}, ANY),
     "base bf16 n3 40x40": ("base", "bf16", 3, 40, 40, {}, ANY),
     "base fp16 n1 default plan": ("base", "fp16", 1, 64, 64, {}, ANY),
@@ -250,19 +232,14 @@ def _out_conv_flavour(eng):
 def _state(r, opts, k, fuse, profile=True):
     """one run under the arm's options: ({label: array}, (flavour tag, ksplit) of out_conv or None).  Read back under the same options: they are part of the plan's key"""
     eng = r.eng
-    try:
-        for k_, v in opts.items():
-            eng.set_option(k_, v)
-        eng.set_option("profile", int(profile)); eng.profile_read(reset=True)
-        x = r.sample(k, fuse=fuse)
-        tag = _out_conv_flavour(eng) if profile and k >= 1 else None
-        eng.set_option("profile", 0); eng.profile_read(reset=True)
+    with pinned(eng, **opts):
+        with pinned(eng, profile=int(profile)):
+            eng.profile_read(reset=True)
+            x = r.sample(k, fuse=fuse)
+            tag = _out_conv_flavour(eng) if profile and k >= 1 else None
+        eng.profile_read(reset=True)
         got = {l: r.read(l) for l in LABELS}
         assert np.array_equal(x.numpy(), got["@x"]) and np.all(np.isfinite(got["@x"]))
-    finally:
-        eng.set_option("profile", 0)
-        for k_ in opts:
-            eng.set_option(k_, DEFAULTS[k_])
     return got, tag
 
 
@@ -320,16 +297,37 @@ def test_two_lanes_equal_the_single_lane_runs_of_their_halves(zoo):
     cfg, m = zoo("base", "bf16")
     r = Run(cfg, m, "bf16", 3, 64, 64, 4, 3, lof=0)
     eng = r.eng
-    try:
-        eng.set_option("dual_stream_min_batch", 2)
+    with pinned(eng, dual_stream=1, dual_stream_min_batch=2):
         both = r.sample(None, fuse=1)
-        eng.set_option("dual_stream", 0)
-        halves = torch.cat([r.sample(None, fuse=1, rows=slice(0, 1)), r.sample(None, fuse=1, rows=slice(1, 3))])
-    finally:
-        eng.set_option("dual_stream", 1); eng.set_option("dual_stream_min_batch", 32)
+        with pinned(eng, dual_stream=0):
+            halves = torch.cat([r.sample(None, fuse=1, rows=slice(0, 1)), r.sample(None, fuse=1, rows=slice(1, 3))])
     d = int((both != halves).sum())
     print(f"\ntwo lanes (1 + 2 tiles) against single-lane runs of the halves: {d} of {both.numel()} elements differ")
     assert torch.isfinite(both).all() and d == 0
+
+
+def test_the_shipped_lane_threshold(zoo):
+    """On the options that ship (dual_stream = 1, dual_stream_min_batch = 32, nothing pinned but the case's own solver order): a batch of n = 33 runs as lanes of
+    n / 2 = 16 and 17 rows and equals, bit for bit, single-lane runs of rows [0, 16) and [16, 33); n = 31 stays below the threshold and equals the unsplit run."""
+    from _engine_opts import SHIPPED
+    assert SHIPPED["dual_stream"] == 1 and SHIPPED["dual_stream_min_batch"] == 32
+    cfg, m = zoo("tiny", "bf16")
+    r = Run(cfg, m, "bf16", 33, 16, 16, 4, 3, lof=0)
+    assert r.eng.get_option("dual_stream", 1) == 1 and r.eng.get_option("dual_stream_min_batch", 32) == 32
+    both = r.sample(None, fuse=1)
+    with pinned(r.eng, dual_stream=0):
+        halves = torch.cat([r.sample(None, fuse=1, rows=slice(0, 16)), r.sample(None, fuse=1, rows=slice(16, 33))])
+        whole = r.sample(None, fuse=1)
+    d = int((both != halves).sum())
+    r31 = Run(cfg, m, "bf16", 31, 16, 16, 4, 3, lof=0)
+    below = r31.sample(None, fuse=1)
+    with pinned(r.eng, dual_stream=0):
+        unsplit = r31.sample(None, fuse=1)
+    d31 = int((below != unsplit).sum())
+    print(f"\nshipped lane threshold: n = 33 against single-lane runs of rows [0, 16) and [16, 33): {d} of {both.numel()} elements differ "
+          f"({int((both != whole).sum())} from the unsplit 33-row run); n = 31 against the unsplit run: {d31} of {below.numel()} differ")
+    assert torch.isfinite(both).all() and torch.isfinite(below).all()
+    assert d == 0 and d31 == 0
 
 
 def test_every_flavour_carried_a_fused_output_conv():

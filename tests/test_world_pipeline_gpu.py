@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from conftest import rel_rms
+from _engine_opts import engine_options_guard, pinned  # noqa: F401  (the guard is an autouse fixture: every test here starts and ends on the shipped options)
 
 pytestmark = pytest.mark.gpu
 
@@ -95,16 +96,13 @@ def test_world_pipeline_get_matches_oracle_composition(td, models):
     assert torch.equal(again["elev"], elev) and torch.equal(again["climate"], clim)
     n0 = w.residual.windows_computed
     w.empty_cache()
-    w.engine.set_option("batch_invariant", 1)
-    try:
+    with pinned(w.engine, batch_invariant=1):
         a = w.get(*box)["elev"]
         w.get(-200, -180, -150, -100, with_climate=False)   # another region first: the windows of `box` are then recomputed in other batches
         w.empty_cache()
         w.get(-21, 13, 27, 77, with_climate=False)          # (a sub-box is NOT the crop of the box: the Laplacian re-encode sees another extent,
         b = w.get(*box)["elev"]                             #  as in the reference; the same box after a flush must give the same bits)
         assert torch.equal(b, a)
-    finally:
-        w.engine.set_option("batch_invariant", 0)
     assert w.residual.windows_computed > n0
     assert w.change_seed(4243) and not w.change_seed(4243)
     assert not torch.equal(w.get(*box, with_climate=False)["elev"], elev)
@@ -265,8 +263,7 @@ def test_request_replica_mode_two_ranks_serve_the_same_world(td, models):
     from terrain_diffusion_amd.engine import get_engine
     from terrain_diffusion_amd.parallel import shard_requests
     eng = get_engine("cuda")
-    eng.set_option("batch_invariant", 1)
-    try:
+    with pinned(eng, batch_invariant=1):
         boxes = [(64 * a - 40, 64 * b + 8, 64 * a + 24, 64 * b + 72) for a in range(3) for b in range(2)]
         one = _world(td, models)
         ref = [one.get(*bx, with_climate=False)["elev"].clone() for bx in boxes]
@@ -280,8 +277,6 @@ def test_request_replica_mode_two_ranks_serve_the_same_world(td, models):
         assert sorted(got) == list(range(len(boxes)))
         for k in range(len(boxes)):
             assert torch.equal(got[k], ref[k]), k
-    finally:
-        eng.set_option("batch_invariant", 0)
 
 
 def test_enqueue_only_cascade_gives_the_bits_of_the_synchronous_one(td, models):
