@@ -20,5 +20,6 @@ from .minecraft import (get_upsampled, classify_biome, get_terrain, minecraft_te
                         parse_minecraft_payload)
 from .explorer import (coarse_channels, colorize, relief_rgba8, raw_tile, land_tiles, coarse_image, coarse_stats, coarse_data,  # noqa: F401
                        detail_image, detail_raw, sample_land_tiles, get_coarse_climate_info, png_bytes)
+from .rivers import relief_overlay_map, smooth_bumps, river_relief_map, smooth_river_bumps  # noqa: F401  (get_relief_map stays relief.py's)
 from .custom_world import (rasterize_cells, fill_nearest, elevation_int16, h_to_meters, fill_nodata, rasterize_layer, azgaar_layers,  # noqa: F401
                            load_and_pad, import_conditioning, export_elevation)

@@ -8,6 +8,7 @@ them on the device per GPU:
     matplotlib itself is not imported,
   * scipy.ndimage.gaussian_filter's 1-D weights (truncate = 4, radius int(4 sigma + 0.5), normalised in float64).
 biome, flow and a caller-supplied rgb image are not supported (no caller of the reference passes them).
+The picture with those three inputs is rivers.get_relief_map (libtd_rivers.so, the same kernels with the overlay branch compiled in).
 """
 import ctypes as C
 import functools

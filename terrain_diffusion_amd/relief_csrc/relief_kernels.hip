@@ -1,9 +1,9 @@
-// Shaded-relief rendering of an elevation image: get_relief_map (terrain_diffusion/inference/relief_map.py:64-199) without biome, flow or a
-// caller-supplied colour image.  Two passes:
+// Shaded-relief rendering of an elevation image: get_relief_map (terrain_diffusion/inference/relief_map.py:64-199).  Two passes:
 //   relief_blur_rows_kernel   scipy gaussian_filter's axis-0 pass for BOTH sigmas from one read of the elevation (NaN fill applied on load,
 //                             mode='reflect'), two fp32 planes out; fused land min / max of the unfilled input for the automatic colour range.
 //   relief_shade_kernel       the axis-1 pass of both blurs on a row tile staged in LDS, np.gradient, the two hillshades, the terrain colormap,
-//                             relief blend, NaN and ocean colouring -> (H, W, 3) fp32.
+//                             relief blend, NaN and ocean colouring -> (H, W, 3) fp32.  A template: <false> is the picture without biome, flow
+//                             or a caller's colours (libtd_relief.so launches only that one), <true> adds those overlays (libtd_rivers.so).
 // Per pixel the elementwise arithmetic is the reference's, in its order and in fp32 with no contraction (numpy does not fuse), through the
 // precise device libm; the blurs accumulate in fp32 in tap order (scipy accumulates in fp64 and stores fp32 between the passes, as here).
 #include <hip/hip_runtime.h>
@@ -40,6 +40,15 @@ struct ReliefParams {
     int has_range;
     int has_fill;
     float fill;          // NaN fill (nanmedian), applied only when has_fill
+};
+
+// The overlays of relief_shade_kernel<true>; a null pointer leaves that overlay out.  relief_shade_kernel<false> ignores the whole struct.
+struct ReliefOverlay {
+    const float* rgb;        // (H, W, 3) base colour in place of the terrain colormap
+    const int* biome;        // (H, W) class ids; where clip(id, 0, 30) > 0 the base colour is palette[id]
+    const float* palette;    // 31 x 3
+    const float* flow;       // (H, W) flow accumulation; a river where flow > flow_threshold
+    float flow_threshold;
 };
 
 __device__ __forceinline__ float relief_fill(float v, int has_fill, float fill) {
@@ -140,10 +149,12 @@ __device__ __forceinline__ float relief_hillshade(float dy, float dx, const Reli
 #define RELIEF_GRAD(i, n, f) ((i) == 0 ? (f(1) - f(0)) : ((i) == (n) - 1 ? (f((n) - 1) - f((n) - 2)) : (f((i) + 1) - f((i) - 1)) / 2.f))
 
 // Pass 2.  Grid (ceil(W / 128), ceil(H / 16)); dynamic LDS = relief_shade_lds_floats(R) floats.
+// With OVERLAY and ov.rgb the colormap and its range are skipped (range_bits may then be null whatever has_range says).
+template <bool OVERLAY>
 __global__ __launch_bounds__(RELIEF_THREADS) void relief_shade_kernel(const float* __restrict__ elev, const float* __restrict__ bl, const float* __restrict__ bs,
                                                                       int H, int W, const float* __restrict__ wl, int rl, const float* __restrict__ ws, int rs,
                                                                       const float* __restrict__ lut, const unsigned* __restrict__ range_bits, ReliefParams p,
-                                                                      float* __restrict__ out) {
+                                                                      ReliefOverlay ov, float* __restrict__ out) {
 #pragma clang fp contract(off)
     extern __shared__ float relief_smem[];
     const int R = rl > rs ? rl : rs;
@@ -186,11 +197,12 @@ __global__ __launch_bounds__(RELIEF_THREADS) void relief_shade_kernel(const floa
     }
     __syncthreads();
     // colour range (step 5 of the reference), resolved here so that the automatic range needs no host round trip
-    double vmin, vmax;
-    if (p.has_range) {
+    const bool colormap = !OVERLAY || !ov.rgb;   // grid-uniform
+    double vmin = 0.0, vmax = 1.0;
+    if (colormap && p.has_range) {
         vmin = p.vmin > 0.0 ? p.vmin : 0.0;
         vmax = p.vmax;
-    } else {
+    } else if (colormap) {
         const float lo = __uint_as_float(~range_bits[0]), hi = __uint_as_float(range_bits[1]);
         vmin = lo;
         vmax = hi;
@@ -205,7 +217,8 @@ __global__ __launch_bounds__(RELIEF_THREADS) void relief_shade_kernel(const floa
         const int ty = q / RELIEF_P2_TX, tx = q - ty * RELIEF_P2_TX;
         const int y = y0 + ty, x = x0 + tx;
         if (y >= H || x >= W) continue;
-        const float e = elev[(size_t)y * W + x];
+        const size_t px = (size_t)y * W + x;
+        const float e = elev[px];
         const bool is_nan = isnan(e);
         const float ef = relief_fill(e, p.has_fill, p.fill);
         // np.gradient of both blurred fields; LDS row (ty+1)+d is image row y+d, column (tx+1)+d is image column x+d
@@ -221,32 +234,58 @@ __global__ __launch_bounds__(RELIEF_THREADS) void relief_shade_kernel(const floa
 #undef FSY
 #undef FSX
         const float hs = powf(relief_clip01(0.75f * hl + 0.25f * hsm), 0.85f);
-        // base colour: terrain colormap of the unfilled land elevation; NaN argument -> the colormap's bad colour (0, 0, 0)
-        const float land = is_nan ? e : (e > 0.f ? e : 0.f);
-        float cm = relief_clip01(powf((land - vmin_f) / den, 0.7f));
-        if (offset) cm = 0.25f + cm * 0.75f;
         float r = 0.f, g = 0.f, b = 0.f;
-        if (!isnan(cm)) {
-            float xi = cm * 256.f;
-            if (xi == 256.f) xi = 255.f;
-            int idx = (int)xi;
-            idx = idx < 0 ? 0 : (idx > 255 ? 255 : idx);   // under / over colours are the first / last entries
-            r = lut_s[idx * 3];
-            g = lut_s[idx * 3 + 1];
-            b = lut_s[idx * 3 + 2];
+        if (colormap) {
+            // base colour: terrain colormap of the unfilled land elevation; NaN argument -> the colormap's bad colour (0, 0, 0)
+            const float land = is_nan ? e : (e > 0.f ? e : 0.f);
+            float cm = relief_clip01(powf((land - vmin_f) / den, 0.7f));
+            if (offset) cm = 0.25f + cm * 0.75f;
+            if (!isnan(cm)) {
+                float xi = cm * 256.f;
+                if (xi == 256.f) xi = 255.f;
+                int idx = (int)xi;
+                idx = idx < 0 ? 0 : (idx > 255 ? 255 : idx);   // under / over colours are the first / last entries
+                r = lut_s[idx * 3];
+                g = lut_s[idx * 3 + 1];
+                b = lut_s[idx * 3 + 2];
+            }
+        } else {
+            r = ov.rgb[px * 3];
+            g = ov.rgb[px * 3 + 1];
+            b = ov.rgb[px * 3 + 2];
+        }
+        if constexpr (OVERLAY) {
+            if (ov.biome) {   // np.where(clip(biome, 0, 30) > 0, palette[biome], base): on top of a caller's rgb too
+                const int id = ov.biome[px];
+                if (id > 0) {
+                    const float* c = ov.palette + (id > 30 ? 30 : id) * 3;
+                    r = c[0];
+                    g = c[1];
+                    b = c[2];
+                }
+            }
         }
         const float m = relief * (0.35f + 0.65f * hs) + omr;
         r = relief_clip01(r * m);
         g = relief_clip01(g * m);
         b = relief_clip01(b * m);
         if (is_nan) r = g = b = __builtin_nanf("");
+        if constexpr (OVERLAY) {
+            // river: 0.25 * shaded + 0.75 * (0.100, 0.450, 0.850), each product rounded to fp32, then one add; a NaN flow compares false,
+            // a river on a NaN pixel stays NaN
+            if (ov.flow && ov.flow[px] > ov.flow_threshold) {
+                r = 0.25f * r + 0.75f * 0.100f;
+                g = 0.25f * g + 0.75f * 0.450f;
+                b = 0.25f * b + 0.75f * 0.850f;
+            }
+        }
         if (ef < 0.f) {   // ocean, on the filled elevation
             const float t = powf(relief_clip01(-ef / 10000.f), 0.7f), u = 1.f - t;
             r = u * 0.68f + t * 0.00f;
             g = u * 0.88f + t * 0.10f;
             b = u * 1.00f + t * 0.45f;
         }
-        float* o = out + ((size_t)y * W + x) * 3;
+        float* o = out + px * 3;
         o[0] = r;
         o[1] = g;
         o[2] = b;
