@@ -185,6 +185,30 @@ int td_sample_edm_img(td_unet* u, int n, int H, int W, int n_steps, const float*
                       const float* cond_img, int cimg_channels, float* x);
 int td_sample_consistency_img(td_unet* u, int n, int H, int W, float t, float sigma_data, const float* sample, const float* z,
                               const float* cond, const float* cond_img, int cimg_channels, float* out);
+/* The EDM sampler with every argument of the reference's decoder sampler (sample_diffusion_decoder.py:44-125) in one struct, so that a later
+ * argument adds a field and not an entry point: conditioning-image channels, autoguidance and score scaling in any combination, on both sampler
+ * lanes.  guide == NULL (guidance_scale is then ignored), score_scaling == 1 and cimg_channels == 0 give td_sample_edm bit for bit; with
+ * cond_img td_sample_edm_img, with a guide td_sample_edm_guided.  A guide reads the same cond_img as the main model.
+ * Score scaling (`_scale_score`, same file :7-40), alpha = score_scaling != 1: in step i the guided-or-plain model output f becomes, at the
+ * current sample x, in fp32 with one rounding per operation in this order,
+ *   v = -sd f;  x0 = x c - v s;  np = x s + v c;  x0a = x + alpha (x0 - x);  va = np c - x0a s;  f' = va / (-sd)
+ * with (c, s) = score_cs_host[2i], [2i+1] = cos t_i, sin t_i, t_i = atan(sigma_i / sigma_data).  The caller computes them (the Python binding with
+ * the reference's torch fp32 ops, so they are its scalars bit for bit); read only when score_scaling != 1.  Such a call runs the solver step as
+ * a kernel of its own (never in the output conv's epilogue), as a guided call does. */
+typedef struct td_edm_ext {
+    int32_t n, H, W, n_steps;
+    const float* sigmas_host;              /* n_steps + 1 (last = 0) */
+    float sigma_data;
+    const float* cond;                     /* [n][cond_row_len], host or device, or NULL for a model without conditional inputs */
+    float* x;                              /* in/out [n][out_channels][H][W], host or device */
+    const float* cond_img;                 /* [n][cimg_channels][H][W], host or device; NULL when cimg_channels == 0 */
+    int32_t cimg_channels;
+    td_unet* guide;                        /* may be NULL */
+    float guidance_scale;
+    float score_scaling;                   /* 1 = off */
+    const float* score_cs_host;            /* n_steps pairs (cos t_i, sin t_i); read only when score_scaling != 1 */
+} td_edm_ext;
+int td_sample_edm_ext(td_unet* u, const td_edm_ext* args);
 
 /* ---- conditioning rows (sample_diffusion_base.py:11-48, process_cond_img) -------------------------------------
  * The 16 + 16 + 4 + 16 + n_hist + 1 conditioning floats of n windows of ONE conditioning grid in one launch.  grid: (7, grid_rows, grid_cols) fp32, host or
@@ -240,6 +264,13 @@ int td_sample_grid_batch(td_unet* u, const td_grid_batch* batch);
 int td_blend_windows(td_engine* e, float* canvas, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts_host,
                      int n_cols, const int32_t* col_starts_host, int n_tiles, const int32_t* wi_host, const int32_t* wj_host,
                      const float* tiles, int accumulate);
+/* The same blend with the caller's weight window (the reference samplers' `weight_window_fn`): window = size*size fp32, host or device, NULL = the
+ * linear window (td_blend_windows is this call with NULL, bit for bit).  Same ascending (wi,wj) summation order.  The window lives in scratch
+ * for the call only.  td_blend_normalize divides as before: where the summed weight is 0 the result is NaN (0 / 0), as `out / out_w` is in
+ * the reference.  td_gather_regions and td_sample_grid_batch keep the linear window. */
+int td_blend_windows_w(td_engine* e, float* canvas, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts_host,
+                       int n_cols, const int32_t* col_starts_host, int n_tiles, const int32_t* wi_host, const int32_t* wj_host,
+                       const float* tiles, int accumulate, const float* window);
 
 /* Many equally sized regions of ONE lazily evaluated window tensor in one launch: what the reference's `InfiniteTensor.__getitem__` does
  * slice by slice when a stage function is handed the argument slices of its windows (infinite_tensor call sites world_pipeline.py:982-992,

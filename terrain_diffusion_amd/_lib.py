@@ -64,6 +64,13 @@ class GridBatch(C.Structure):
                 ("col_starts_host", _P), ("wi_host", _P), ("wj_host", _P), ("windows_out", _P)]
 
 
+class EdmExt(C.Structure):
+    """td_edm_ext (include/td_engine.h): the arguments of td_sample_edm_ext"""
+    _fields_ = [("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_steps", C.c_int32), ("sigmas_host", _P), ("sigma_data", C.c_float), ("cond", _P),
+                ("x", _P), ("cond_img", _P), ("cimg_channels", C.c_int32), ("guide", _P), ("guidance_scale", C.c_float), ("score_scaling", C.c_float),
+                ("score_cs_host", _P)]
+
+
 _SIGS = {
     "td_last_error": (C.c_char_p, []),
     "td_version": (C.c_int, []),
@@ -98,8 +105,10 @@ _SIGS = {
     "td_sample_edm_guided": (C.c_int, [_P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P]),
     "td_sample_consistency": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P]),
     "td_sample_edm_img": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, C.c_int, _P]),
+    "td_sample_edm_ext": (C.c_int, [_P, C.POINTER(EdmExt)]),
     "td_sample_consistency_img": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int, _P]),
     "td_blend_windows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int]),
+    "td_blend_windows_w": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
     "td_gather_regions": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "td_blend_normalize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "td_linear_weight_window": (C.c_int, [_P, C.c_int, _P]),

@@ -328,6 +328,8 @@ struct Plan {
     const void* graph_guide = nullptr;       // guide plan / its modulation buffer / scale the captured graph was built with (autoguidance)
     const void* graph_guide_cvec = nullptr;
     float graph_gscale = 0.f;
+    float graph_alpha = 1.f;                 // score-scaling factor and the (cos t_i, sin t_i) pairs baked into the captured graph's kernel arguments
+    std::vector<float> graph_cs;
     size_t bytes = 0;          // device memory owned by this plan (activations, partials, sampler state)
     uint64_t last_use = 0;     // LRU stamp (td_unet::use_clock)
     void drop_graph() { if (graph) { (void)hipGraphExecDestroy(graph); graph = nullptr; } }
@@ -1593,10 +1595,13 @@ static int stage_cond_img(td_unet* u, Plan& pl, int n, int HW, const float* cond
     return TD_OK;
 }
 
+// score scaling of a sampler call (td_sample_edm_ext): alpha == 1 is off and reads nothing else
+struct ScoreArgs { float alpha = 1.f; const float* cs_host = nullptr; };
+
 // One lane of the batched EDM sampler: everything is enqueued on e->stream (the caller swaps the engine's streams for the second lane) and
 // NOT waited for; temporaries that must outlive the queue go to `hold`.
 static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
-                           const float* cond, const float* cond_img, int cimg, float* x, int lane, std::vector<Buf>& hold) {
+                           const float* cond, const float* cond_img, int cimg, float* x, int lane, std::vector<Buf>& hold, const ScoreArgs& sa) {
     if (guide) {
         if (!guide->finalized) return fail(TD_ERR_STATE, "finalize the guide model first");
         if (guide->eng != u->eng || guide->dt != u->dt) return fail(TD_ERR_ARG, "guide model must live on the same engine and use the same dtype");
@@ -1605,6 +1610,10 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
     }
     if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
     if (n_steps < 1) return fail(TD_ERR_ARG, "n_steps");
+    const float alpha = sa.alpha;
+    if (alpha != 1.f && !sa.cs_host) return fail(TD_ERR_ARG, "score_scaling != 1 needs score_cs_host (n_steps pairs cos t_i, sin t_i)");
+    if (!std::isfinite(alpha)) return fail(TD_ERR_ARG, "score_scaling must be finite");
+    const std::vector<float> cs = alpha != 1.f ? std::vector<float>(sa.cs_host, sa.cs_host + 2 * (size_t)n_steps) : std::vector<float>();
     Plan* pl;
     int rc = build_plan(u, n, H, W, &pl, lane);
     if (rc) return rc;
@@ -1654,13 +1663,18 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
         // north_star: "the per-tile EDM scheduler step fused into the epilogue".  Without a guide model the solver update of step i runs in the
         // epilogue of the U-Net's output conv (option "fuse_solver", default on; bit-identical to the separate kernel: same arithmetic on the same
         // fp32 F); with autoguidance the update needs BOTH models' outputs and stays a kernel of its own.
-        const bool fuse = !gpl && e->option("fuse_solver", 1) != 0 && pl->ops.back().kind == Op::CONV && pl->ops.back().p.epi == EPI_PLAIN && pl->ops.back().p.out_f32;
+        const bool fuse = !gpl && alpha == 1.f && e->option("fuse_solver", 1) != 0 && pl->ops.back().kind == Op::CONV && pl->ops.back().p.epi == EPI_PLAIN && pl->ops.back().p.out_f32;
         for (int i = 0; i < n_run; ++i) {
             int r = run_unet(u, *pl, i, fuse ? &ks[i] : nullptr);
             if (r) return r;
             if (fuse) continue;
             if (gpl && (r = run_unet(guide, *gpl, i))) return r;
-            TD_DISPATCH_T(u, hipLaunchKernelGGL(dpm_step_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, (float*)pl->x->p, (float*)pl->m1->p, (const float*)pl->F, (T_*)pl->xin, n, C, HW, 8, u->chunk, ks[i], Fg, gscale, gpl ? (T_*)gpl->xin : (T_*)nullptr, solver_order == 3 ? (float*)pl->m2->p : (float*)nullptr));
+            if (alpha == 1.f) {
+                TD_DISPATCH_T(u, hipLaunchKernelGGL(dpm_step_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, (float*)pl->x->p, (float*)pl->m1->p, (const float*)pl->F, (T_*)pl->xin, n, C, HW, 8, u->chunk, ks[i], Fg, gscale, gpl ? (T_*)gpl->xin : (T_*)nullptr, solver_order == 3 ? (float*)pl->m2->p : (float*)nullptr));
+            } else {   // score scaling: the compile-time variant of the same step, scalars of step i from the caller's table
+                const ScoreScale ss{alpha, cs[2 * i], cs[2 * i + 1], -sigma_data};
+                TD_DISPATCH_T(u, hipLaunchKernelGGL(dpm_step_ss_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, (float*)pl->x->p, (float*)pl->m1->p, (const float*)pl->F, (T_*)pl->xin, n, C, HW, 8, u->chunk, ks[i], Fg, gscale, gpl ? (T_*)gpl->xin : (T_*)nullptr, solver_order == 3 ? (float*)pl->m2->p : (float*)nullptr, ss));
+            }
         }
         HIP_TRY(hipGetLastError());
         return TD_OK;
@@ -1673,7 +1687,7 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
         const void* gkey = gpl ? (const void*)gpl->cvec->p : nullptr;
         if (!pl->graph || pl->graph_sigmas != sg || pl->graph_sigma_data != sigma_data || pl->graph_solver_order != solver_order || pl->graph_lof != (int)lof ||
             pl->graph_guide != (const void*)gpl || pl->graph_guide_cvec != gkey || pl->graph_gscale != gscale || pl->graph_fuse != (int)e->option("fuse_solver", 1) ||
-            pl->graph_stop != stop_after) {
+            pl->graph_stop != stop_after || pl->graph_alpha != alpha || pl->graph_cs != cs) {
             pl->drop_graph();
             hipGraph_t g = nullptr;
             HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -1687,6 +1701,7 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
             pl->graph_sigmas = sg; pl->graph_sigma_data = sigma_data; pl->graph_solver_order = solver_order; pl->graph_lof = (int)lof; pl->graph_fuse = (int)e->option("fuse_solver", 1);
             pl->graph_stop = stop_after;
             pl->graph_guide = gpl; pl->graph_guide_cvec = gkey; pl->graph_gscale = gscale;
+            pl->graph_alpha = alpha; pl->graph_cs = cs;
         }
         HIP_TRY(hipGraphLaunch(pl->graph, st));
     } else if ((rc = enqueue())) return rc;
@@ -1706,23 +1721,23 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
 // like a single-lane one: results ordered on the engine's stream, enqueue-only under option "async".
 // The sampler's body, enqueue-only: one lane or two on the engine's streams, ending ordered on e->stream.  On failure both streams are drained.
 static int sample_edm_enqueue(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
-                              const float* cond, const float* cond_img, int cimg, float* x, std::vector<Buf>& hold) {
+                              const float* cond, const float* cond_img, int cimg, float* x, std::vector<Buf>& hold, const ScoreArgs& sa = ScoreArgs()) {
     td_engine* e = u->eng;
     const bool dual = e->stream2 && e->option("dual_stream", 1) != 0 && n >= std::max<int64_t>(2, e->option("dual_stream_min_batch", 32));
     const bool concurrent = e->option("profile", 0) == 0;  // profile mode times every launch with events on ONE stream: the lanes run one after the other
     if (!dual) {
-        int rc = sample_edm_lane(u, guide, gscale, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, 0, hold);
+        int rc = sample_edm_lane(u, guide, gscale, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, 0, hold, sa);
         if (rc) (void)hipStreamSynchronize(e->stream);
         return rc;
     }
     const int nA = n / 2, nB = n - nA, C = u->cfg.out_channels;
     const size_t HW = (size_t)H * W;
     if (concurrent) { HIP_TRY(hipEventRecord(e->ev_fork, e->stream)); HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_fork, 0)); }
-    int rc = sample_edm_lane(u, guide, gscale, nA, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, 0, hold);
+    int rc = sample_edm_lane(u, guide, gscale, nA, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, 0, hold, sa);
     if (!rc) {
         if (concurrent) std::swap(e->stream, e->stream2);
         rc = sample_edm_lane(u, guide, gscale, nB, H, W, n_steps, sigmas_host, sigma_data, cond ? cond + (size_t)nA * u->cond_row_len : nullptr,
-                             cond_img ? cond_img + (size_t)nA * cimg * HW : nullptr, cimg, x + (size_t)nA * C * HW, 1, hold);
+                             cond_img ? cond_img + (size_t)nA * cimg * HW : nullptr, cimg, x + (size_t)nA * C * HW, 1, hold, sa);
         if (concurrent) std::swap(e->stream, e->stream2);
     }
     if (rc) { (void)hipStreamSynchronize(e->stream); (void)hipStreamSynchronize(e->stream2); return rc; }
@@ -1731,12 +1746,12 @@ static int sample_edm_enqueue(td_unet* u, td_unet* guide, float gscale, int n, i
 }
 
 static int sample_edm_impl(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
-                           const float* cond, const float* cond_img, int cimg, float* x) {
+                           const float* cond, const float* cond_img, int cimg, float* x, const ScoreArgs& sa = ScoreArgs()) {
     td_engine* e = u->eng;
     DevGuard dg_(e->device);
     std::vector<Buf> hold;
     const bool all_dev = is_device_ptr(x) && (!cond || is_device_ptr(cond)) && (!cond_img || is_device_ptr(cond_img));
-    int rc = sample_edm_enqueue(u, guide, gscale, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, hold);
+    int rc = sample_edm_enqueue(u, guide, gscale, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, hold, sa);
     if (rc) return rc;
     // default: results complete on return (the caller's framework uses other streams); option "async": left enqueued on e->stream
     return end_call(e, hold, all_dev);
@@ -1753,6 +1768,18 @@ int td_sample_edm_guided(td_unet* u, td_unet* guide, float guidance_scale, int n
                          const float* cond, float* x) {
     if (!guide) return fail(TD_ERR_ARG, "null guide model");
     return sample_edm_impl(u, guide, guidance_scale, n, H, W, n_steps, sigmas_host, sigma_data, cond, nullptr, 0, x);
+}
+
+// Every argument of the EDM sampler in one struct: conditioning-image channels, a guide model and score scaling in any combination.  With no
+// guide (or scale 1), score_scaling == 1 it is the call td_sample_edm_img makes; the guide's plan gets the same cond_img staged as the main one.
+int td_sample_edm_ext(td_unet* u, const td_edm_ext* a) {
+    if (!u || !a) return fail(TD_ERR_ARG, "td_sample_edm_ext: null argument");
+    if (!a->sigmas_host || !a->x) return fail(TD_ERR_ARG, "td_sample_edm_ext: sigmas_host / x is null");
+    if (a->cimg_channels < 0 || (a->cimg_channels > 0 && !a->cond_img)) return fail(TD_ERR_ARG, "td_sample_edm_ext: cond_img is null");
+    ScoreArgs sa;
+    sa.alpha = a->score_scaling; sa.cs_host = a->score_cs_host;
+    return sample_edm_impl(u, a->guide, a->guide ? a->guidance_scale : 1.f, a->n, a->H, a->W, a->n_steps, a->sigmas_host, a->sigma_data, a->cond,
+                           a->cimg_channels > 0 ? a->cond_img : nullptr, a->cimg_channels, a->x, sa);
 }
 
 int td_sample_consistency_img(td_unet* u, int n, int H, int W, float t, float sigma_data, const float* sample, const float* z, const float* cond,
@@ -1911,7 +1938,7 @@ struct BlendJob {
     Buf drow, dcol, drs, dcs, dtof, dww;
 };
 static int blend_prepare(td_engine* e, BlendJob& j, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols, const int32_t* col_starts,
-                         int n_tiles, const int32_t* wi, const int32_t* wj) {
+                         int n_tiles, const int32_t* wi, const int32_t* wj, const float* window = nullptr) {
     if (C + 1 > 8) return fail(TD_ERR_UNSUPPORTED, "C+1 must be <= 8");
     std::vector<int>& rowmap = j.rowmap; std::vector<int>& colmap = j.colmap; std::vector<int>& tile_of = j.tile_of;
     rowmap.assign((size_t)Hc * 4, -1); colmap.assign((size_t)Wc * 4, -1); tile_of.assign((size_t)n_rows * n_cols, -1);
@@ -1933,7 +1960,12 @@ static int blend_prepare(td_engine* e, BlendJob& j, int C, int Hc, int Wc, int s
         if (wi[i] < 0 || wi[i] >= n_rows || wj[i] < 0 || wj[i] >= n_cols) return fail(TD_ERR_ARG, "window index out of range");
         tile_of[(size_t)wi[i] * n_cols + wj[i]] = i;
     }
-    weight_window_host(size, j.ww);
+    // a caller's window (td_blend_windows_w) goes to this job's scratch like the linear one: never into the per-size cache e->wwin, which is keyed by size only
+    if (!window) weight_window_host(size, j.ww);
+    else {
+        j.ww.resize((size_t)size * size);
+        HIP_TRY(hipMemcpy(j.ww.data(), window, j.ww.size() * 4, is_device_ptr(window) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    }
     auto up = [&](const void* src, size_t bytes, Buf& b) -> int {
         b.reset(new DevBuf());
         HIP_TRY(b->scratch(e->scratch, bytes));
@@ -1954,11 +1986,16 @@ static int blend_enqueue(td_engine* e, const BlendJob& j, float* dcanvas, int C,
 
 int td_blend_windows(td_engine* e, float* canvas, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols,
                      const int32_t* col_starts, int n_tiles, const int32_t* wi, const int32_t* wj, const float* tiles, int accumulate) {
+    return td_blend_windows_w(e, canvas, C, Hc, Wc, size, n_rows, row_starts, n_cols, col_starts, n_tiles, wi, wj, tiles, accumulate, nullptr);
+}
+
+int td_blend_windows_w(td_engine* e, float* canvas, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols,
+                       const int32_t* col_starts, int n_tiles, const int32_t* wi, const int32_t* wj, const float* tiles, int accumulate, const float* window) {
     DevGuard dg_(e->device);
     hipStream_t st = e->stream;
     BlendJob j;
     int rc;
-    if ((rc = blend_prepare(e, j, C, Hc, Wc, size, n_rows, row_starts, n_cols, col_starts, n_tiles, wi, wj))) return rc;
+    if ((rc = blend_prepare(e, j, C, Hc, Wc, size, n_rows, row_starts, n_cols, col_starts, n_tiles, wi, wj, window))) return rc;
     std::vector<Buf> hold;
     const void* dt;
     if ((rc = to_device(e, tiles, (size_t)n_tiles * C * size * size * 4, hold, &dt))) return rc;

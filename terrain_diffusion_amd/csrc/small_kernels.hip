@@ -265,10 +265,12 @@ __global__ void unpack_output_kernel(const float* __restrict__ F, float* __restr
 
 // One DPM-Solver++(2M) step (dpmsolver.py:245-258, 454-561, 650-726) fused with the next step's input
 // preconditioning (dpmsolver.py:226-229).  x, m1 planar fp32 [N][C][HW]; F NHWC fp32.
-template <typename T>
-__global__ void dpm_step_kernel(float* __restrict__ x, float* __restrict__ m1, const float* __restrict__ F, T* __restrict__ xin,
-                                int N, int C, int HW, int fstride, int cstride, SchedCoef k, const float* __restrict__ Fg, float gscale,
-                                T* __restrict__ xin2, float* __restrict__ m2) {
+// SS (score scaling, sample_diffusion_decoder.py:7-40 `_scale_score`, alpha != 1) is a compile-time variant: the SS = false body is the kernel as it
+// was, and the scaled step is a kernel of its own (dpm_step_ss_kernel) so that the plain kernel keeps its argument list too.
+template <typename T, bool SS>
+__device__ __forceinline__ void dpm_step_body(float* __restrict__ x, float* __restrict__ m1, const float* __restrict__ F, T* __restrict__ xin,
+                                              int N, int C, int HW, int fstride, int cstride, const SchedCoef& k, const float* __restrict__ Fg, float gscale,
+                                              T* __restrict__ xin2, float* __restrict__ m2, const ScoreScale& ss) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)N * HW) return;
     int n = (int)(i / HW), p = (int)(i % HW);
@@ -277,6 +279,7 @@ __global__ void dpm_step_kernel(float* __restrict__ x, float* __restrict__ m1, c
         float xs = x[xi];
         float f = F[i * fstride + c];
         if (Fg) { const float g = Fg[i * fstride + c]; f = g + gscale * (f - g); }  // autoguidance (sample_diffusion_base.py:107-110,155-160)
+        if (SS) f = scale_score(ss, xs, f);   // on the guided-or-plain output, before the update (sample_diffusion_decoder.py:119)
         float xn, m0;
         const float m1v = (k.order == 1 && !m2) ? 0.f : m1[xi];
         dpm_update(k, xs, f, m1v, k.order == 3 ? m2[xi] : 0.f, xn, m0);
@@ -289,6 +292,18 @@ __global__ void dpm_step_kernel(float* __restrict__ x, float* __restrict__ m1, c
             if (xin2) xin2[i * cstride + c] = xs_next;  // the guide model's input buffer
         }
     }
+}
+template <typename T>
+__global__ void dpm_step_kernel(float* __restrict__ x, float* __restrict__ m1, const float* __restrict__ F, T* __restrict__ xin,
+                                int N, int C, int HW, int fstride, int cstride, SchedCoef k, const float* __restrict__ Fg, float gscale,
+                                T* __restrict__ xin2, float* __restrict__ m2) {
+    dpm_step_body<T, false>(x, m1, F, xin, N, C, HW, fstride, cstride, k, Fg, gscale, xin2, m2, ScoreScale{});
+}
+template <typename T>
+__global__ void dpm_step_ss_kernel(float* __restrict__ x, float* __restrict__ m1, const float* __restrict__ F, T* __restrict__ xin,
+                                   int N, int C, int HW, int fstride, int cstride, SchedCoef k, const float* __restrict__ Fg, float gscale,
+                                   T* __restrict__ xin2, float* __restrict__ m2, ScoreScale ss) {
+    dpm_step_body<T, true>(x, m1, F, xin, N, C, HW, fstride, cstride, k, Fg, gscale, xin2, m2, ss);
 }
 
 // Trig-flow consistency step (world_pipeline.py:1097-1129 / sample_diffusion_base.py:251-257):
@@ -555,6 +570,9 @@ template __global__ void write_cond_img_kernel<_Float16>(const float*, _Float16*
 template __global__ void dpm_step_kernel<float>(float*, float*, const float*, float*, int, int, int, int, int, SchedCoef, const float*, float, float*, float*);
 template __global__ void dpm_step_kernel<__bf16>(float*, float*, const float*, __bf16*, int, int, int, int, int, SchedCoef, const float*, float, __bf16*, float*);
 template __global__ void dpm_step_kernel<_Float16>(float*, float*, const float*, _Float16*, int, int, int, int, int, SchedCoef, const float*, float, _Float16*, float*);
+template __global__ void dpm_step_ss_kernel<float>(float*, float*, const float*, float*, int, int, int, int, int, SchedCoef, const float*, float, float*, float*, ScoreScale);
+template __global__ void dpm_step_ss_kernel<__bf16>(float*, float*, const float*, __bf16*, int, int, int, int, int, SchedCoef, const float*, float, __bf16*, float*, ScoreScale);
+template __global__ void dpm_step_ss_kernel<_Float16>(float*, float*, const float*, _Float16*, int, int, int, int, int, SchedCoef, const float*, float, _Float16*, float*, ScoreScale);
 template __global__ void consistency_pre_kernel<float>(const float*, const float*, float*, float*, int, int, int, int, float, float, float, int);
 template __global__ void consistency_pre_kernel<__bf16>(const float*, const float*, float*, __bf16*, int, int, int, int, float, float, float, int);
 template __global__ void consistency_pre_kernel<_Float16>(const float*, const float*, float*, _Float16*, int, int, int, int, float, float, float, int);

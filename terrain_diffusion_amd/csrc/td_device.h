@@ -46,6 +46,21 @@ __device__ __forceinline__ void dpm_update(const SchedCoef& k, float xs, float f
     }
 }
 
+// EDM score scaling (sample_diffusion_decoder.py:7-40, `_scale_score` with alpha != 1) of one model output f at the current sample x: the trig-flow
+// x0 prediction is pushed alpha times as far from x, and the velocity is rebuilt from it.  c, s = cos t, sin t of t = atan(sigma / sigma_data) come
+// from the host (the caller's torch fp32 ops: the reference's scalars bit for bit, no device libm); neg_sd = -sigma_data.  One fp32 rounding per
+// operation in the reference's order: the reference evaluates each line with a tensor op of its own, so nothing here may contract into an FMA.
+struct ScoreScale { float alpha, c, s, neg_sd; };
+__device__ __forceinline__ float scale_score(const ScoreScale& q, float x, float f) {
+#pragma clang fp contract(off)
+    const float v = q.neg_sd * f;
+    const float x0 = x * q.c - v * q.s;
+    const float np = x * q.s + v * q.c;
+    const float x0a = x + q.alpha * (x0 - x);
+    const float va = np * q.c - x0a * q.s;
+    return va / q.neg_sd;
+}
+
 // a * b rounded to fp32 and THEN to the storage type, as the reference does (an fp32 product, then the cast).  Left to itself the compiler fuses the multiply into the
 // fp16 conversion (v_fma_mixlo_f16: ONE rounding of the exact product), which differs from the spelled arithmetic wherever the fp32 product lands on an fp16 tie
 // (found on the MI355X by tests/test_sampler_ops_gpu.py: 1 element in ~10^4 of the fp16 model input, one fp16 ulp).  The empty asm keeps the product in a register.

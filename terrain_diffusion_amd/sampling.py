@@ -13,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import lib, check, GridBatch
+from ._lib import lib, check, GridBatch, EdmExt
 from .engine import ptr
 from . import noise as _noise
 
@@ -188,13 +188,33 @@ def tile_conditioning_rows(engine, cond_inputs, tiles, histogram_raw, cond_means
     return cond_rows(engine, cond_inputs, tiles, histogram_raw, cond_means, cond_stds, noise_level, args=args)
 
 
-def blend_windows(engine, canvas, tiles, tile_idx, h_starts, w_starts, size, accumulate=True):
-    """canvas (C+1,Hc,Wc) += windows (deterministic gather, reference loop order)."""
+def _weight_window(weight_window_fn, size, device):
+    """The reference samplers' `weight_window_fn(size, device, dtype) -> [1,1,S,S]`, called once as they call it (fp32 here), as the host array
+    td_blend_windows_w takes; None (the linear window) stays None.  A window the blend cannot mean is refused: wrong shape, NaN / inf, negative weights."""
+    if weight_window_fn is None:
+        return None
+    w = torch.as_tensor(weight_window_fn(int(size), device, torch.float32))
+    if tuple(w.shape) != (1, 1, int(size), int(size)):
+        raise ValueError(f"weight_window_fn must return a [1, 1, {size}, {size}] tensor, got {tuple(w.shape)}")
+    w = np.ascontiguousarray(w.detach().to(device="cpu", dtype=torch.float32).numpy().reshape(int(size), int(size)))
+    if not np.all(np.isfinite(w)):
+        raise ValueError("weight_window_fn returned NaN or infinite weights")
+    if np.any(w < 0):
+        raise ValueError("weight_window_fn returned negative weights")
+    return w
+
+
+def blend_windows(engine, canvas, tiles, tile_idx, h_starts, w_starts, size, accumulate=True, window=None):
+    """canvas (C+1,Hc,Wc) += windows (deterministic gather, reference loop order).  window: (size, size) fp32 host array (_weight_window), None = linear."""
     C_, Hc, Wc = canvas.shape[0] - 1, canvas.shape[1], canvas.shape[2]
     rs = np.asarray(h_starts, dtype=np.int32)
     cs = np.asarray(w_starts, dtype=np.int32)
     wi = np.asarray([t[0] for t in tile_idx], dtype=np.int32)
     wj = np.asarray([t[1] for t in tile_idx], dtype=np.int32)
+    if window is not None:
+        check(lib().td_blend_windows_w(engine._h, ptr(canvas), C_, Hc, Wc, size, len(rs), C.c_void_p(rs.ctypes.data), len(cs), C.c_void_p(cs.ctypes.data),
+                                       len(wi), C.c_void_p(wi.ctypes.data), C.c_void_p(wj.ctypes.data), ptr(tiles), int(accumulate), C.c_void_p(window.ctypes.data)))
+        return canvas
     check(lib().td_blend_windows(engine._h, ptr(canvas), C_, Hc, Wc, size, len(rs), C.c_void_p(rs.ctypes.data), len(cs), C.c_void_p(cs.ctypes.data),
                                  len(wi), C.c_void_p(wi.ctypes.data), C.c_void_p(wj.ctypes.data), ptr(tiles), int(accumulate)))
     return canvas
@@ -208,18 +228,35 @@ def blend_normalize(engine, canvas, scale=1.0):
 
 
 @torch.no_grad()
-def sample_tiles_edm(model, scheduler, x, cond, steps, cond_img=None, guide_model=None, guidance_scale=1.0):
+def score_scaling_table(sigmas, sigma_data):
+    """(cos t_i, sin t_i), t_i = atan(sigma_i / sigma_data), per step as `_scale_score` computes them (sample_diffusion_decoder.py:33-35): the same torch
+    fp32 CPU ops on the scheduler's fp32 sigmas, so the scalars are the reference's bit for bit.  (n_steps, 2) fp32 array for td_edm_ext.score_cs_host."""
+    sig = torch.as_tensor(sigmas, dtype=torch.float32).cpu()[:-1]
+    t = torch.atan(sig / torch.as_tensor(float(sigma_data), dtype=torch.float32))
+    return np.ascontiguousarray(torch.stack([torch.cos(t), torch.sin(t)], dim=1).numpy())
+
+
+@torch.no_grad()
+def sample_tiles_edm(model, scheduler, x, cond, steps, cond_img=None, guide_model=None, guidance_scale=1.0, score_scaling=1.0):
     """Runs `steps` DPM-Solver++ steps on a batch of independent tiles (device tensor x: [n,C,H,W], scaled noise). In place.
     cond_img: optional [n,Cc,H,W] conditioning-image channels concatenated after the sample channels in the model input
-    (coarse stage: world_pipeline.py:946 `torch.cat([scaled_in, cond_img], dim=1)`)."""
+    (coarse stage: world_pipeline.py:946 `torch.cat([scaled_in, cond_img], dim=1)`).
+    score_scaling: `_scale_score`'s alpha (sample_diffusion_decoder.py:7-40, 1 = off).  A guide together with cond_img, or alpha != 1, goes through
+    td_sample_edm_ext; every other call is the one it was."""
     scheduler.set_timesteps(steps)
     sig = scheduler.sigmas.to(torch.float32).cpu().contiguous()
     n, _, H, W = x.shape
     cimg = 0 if cond_img is None else cond_img.shape[1]
     with _solver_options(model.engine, scheduler):
-        if guide_model is not None and guidance_scale != 1.0:   # autoguidance (sample_diffusion_base.py:105-110)
-            if cond_img is not None:
-                raise NotImplementedError("autoguidance with conditioning-image channels")
+        guided = guide_model is not None and guidance_scale != 1.0
+        if (guided and cond_img is not None) or float(score_scaling) != 1.0:
+            cs = score_scaling_table(sig, scheduler.config.sigma_data) if float(score_scaling) != 1.0 else None
+            a = EdmExt(n=n, H=H, W=W, n_steps=steps, sigmas_host=ptr(sig), sigma_data=float(scheduler.config.sigma_data), cond=ptr(cond), x=ptr(x),
+                       cond_img=ptr(cond_img), cimg_channels=cimg, guide=guide_model._h if guided else None, guidance_scale=float(guidance_scale),
+                       score_scaling=float(score_scaling), score_cs_host=None if cs is None else C.c_void_p(cs.ctypes.data))
+            check(lib().td_sample_edm_ext(model._h, C.byref(a)))
+            return x
+        if guided:   # autoguidance (sample_diffusion_base.py:105-110)
             check(lib().td_sample_edm_guided(model._h, guide_model._h, float(guidance_scale), n, H, W, steps, ptr(sig), float(scheduler.config.sigma_data), ptr(cond), ptr(x)))
             return x
         check(lib().td_sample_edm_img(model._h, n, H, W, steps, ptr(sig), float(scheduler.config.sigma_data), ptr(cond), ptr(cond_img), cimg, ptr(x)))
@@ -246,12 +283,11 @@ def sample_base_diffusion(model, scheduler, shape, cond_inputs, *, cond_means, c
     `tiles`: optional subset of (ic, jc) window indices to run (multi-GPU sharding); `return_canvas` returns the
     un-normalised (C+1,H,W) accumulator instead of output/weights/sigma_data; `return_windows` additionally returns the
     pre-blend window outputs [(ic, jc)] -> (C, T, T) device tensors (parity tests look at windows before the blend mixes them)."""
-    if weight_window_fn is not None:
-        raise NotImplementedError("custom weight windows")
     B, C_, H, W = shape
     if B != 1:
         raise NotImplementedError("B == 1 (one canvas) per call")
     eng, dev = model.engine, model.device
+    window = _weight_window(weight_window_fn, tile_size, dev) if tile_size is not None else None
     sd = float(scheduler.config.sigma_data)
     scheduler.set_timesteps(steps)
     sigma0 = float(scheduler.sigmas[0])
@@ -275,7 +311,9 @@ def sample_base_diffusion(model, scheduler, shape, cond_inputs, *, cond_means, c
     # the blend enqueued back to back, one wait) instead of four calls with the conditioning rows built window by window on the host in between;
     # autoguidance and conditioning shapes td_cond_rows does not cover stay on the four calls
     grid_args = _cond_grid_args(cond_inputs, histogram_raw, cond_means, cond_stds, noise_level) if cond_inputs.ndim == 4 else None
-    fused = eng.get_option("grid_fused", 1) != 0 and (guide_model is None or guidance_scale == 1.0) and (cond_inputs.ndim == 1 or grid_args is not None)
+    # a custom weight window takes the four calls too: td_sample_grid_batch blends with the linear window (its struct layout is ABI)
+    fused = (eng.get_option("grid_fused", 1) != 0 and (guide_model is None or guidance_scale == 1.0) and (cond_inputs.ndim == 1 or grid_args is not None)
+             and weight_window_fn is None)
     # initial_noise[..., i0:i1, j0:j1] of one shared field (sample_diffusion_base.py:124,145) == windows of the absolute field
     # the bounded sampler's noise field is this package's own convention (the reference draws torch.randn here): 64x64 noise tiles,
     # or one tile size that holds the window when the window is larger
@@ -315,7 +353,7 @@ def sample_base_diffusion(model, scheduler, shape, cond_inputs, *, cond_means, c
         if return_windows:
             windows.update({t: x[k].clone() for k, t in enumerate(chunk)})
         if not fused:
-            blend_windows(eng, canvas, x, chunk, h_starts, w_starts, tile_size, accumulate=True)
+            blend_windows(eng, canvas, x, chunk, h_starts, w_starts, tile_size, accumulate=True, window=window)
     out = canvas if return_canvas else blend_normalize(eng, canvas, 1.0 / sd)[None]
     return (out, windows) if return_windows else out
 
@@ -349,9 +387,10 @@ def sample_base_consistency(model, scheduler, shape, cond_inputs, *, cond_means,
                             noise_seed=42 + 5819, noise_origin=(0, 0), max_batch=64):
     """sample_diffusion_base.py:171-268: trig-flow consistency phases, blend between phases (the InfiniteDiffusion pattern)."""
     B, C_, H, W = shape
-    if B != 1 or tile_size is None or weight_window_fn is not None:
+    if B != 1 or tile_size is None:
         raise NotImplementedError
     eng, dev = model.engine, model.device
+    window = _weight_window(weight_window_fn, tile_size, dev)
     sd = float(scheduler.config.sigma_data)
     init_t = math.atan(float(scheduler.config.sigma_max) / sd) if noise is None else None
     sigma0 = scheduler.sigmas[0] if noise is not None else None
@@ -379,7 +418,7 @@ def sample_base_consistency(model, scheduler, shape, cond_inputs, *, cond_means,
             out = torch.empty_like(z)
             cond = cond_all[sl].contiguous()
             check(lib().td_sample_consistency(model._h, z.shape[0], tile_size, tile_size, float(t), sd, ptr(prev), ptr(z), ptr(cond), ptr(out)))
-            blend_windows(eng, canvas, out, tiles[sl], h_starts, w_starts, tile_size, accumulate=True)
+            blend_windows(eng, canvas, out, tiles[sl], h_starts, w_starts, tile_size, accumulate=True, window=window)
         sample = blend_normalize(eng, canvas, 1.0)
     return (sample / sd)[None]
 
@@ -396,13 +435,13 @@ def _cond_tiles(cond_img, h, w, device):
     return cond_img.contiguous()
 
 
-def _blend_batch(eng, tiles, b, n_tiles, tile_idx, h_starts, w_starts, tile_size, h, w, scale):
+def _blend_batch(eng, tiles, b, n_tiles, tile_idx, h_starts, w_starts, tile_size, h, w, scale, window=None):
     """tiles (n_tiles*b, C, T, T) ordered tile-major, batch-minor -> (b, C, h, w): out / out_w of the reference loops, times `scale`."""
     C_ = tiles.shape[1]
     outs = []
     for k in range(b):
         canvas = torch.zeros((C_ + 1, h, w), dtype=torch.float32, device=tiles.device)
-        blend_windows(eng, canvas, tiles[k::b].contiguous(), tile_idx, h_starts, w_starts, tile_size, accumulate=False)
+        blend_windows(eng, canvas, tiles[k::b].contiguous(), tile_idx, h_starts, w_starts, tile_size, accumulate=False, window=window)
         outs.append(blend_normalize(eng, canvas, scale))
     return torch.stack(outs)
 
@@ -420,12 +459,8 @@ def sample_decoder_diffusion_tiled(model, scheduler, cond_img, noise, tile_size=
                                    guidance_scale=1.0, score_scaling=1.0, weight_window_fn=None, max_batch=64):
     """sample_diffusion_decoder.py:44-125: tiled conditional EDM sampling of a decoder model.  `noise` is the initial sample as the caller
     scaled it (the reference uses it as is), `cond_img` is concatenated after the sample channels.  Returns out / out_w (no sigma_data
-    division -- the reference has none here).  Not supported (raise): a guide model together with conditioning-image channels, score scaling
-    other than 1, custom weight windows."""
-    if weight_window_fn is not None or score_scaling != 1.0:
-        raise NotImplementedError("custom weight windows / score scaling")
-    if guidance_model is not None and guidance_scale != 1.0:
-        raise NotImplementedError("autoguidance with conditioning-image channels")
+    division -- the reference has none here).  `guidance_model` / `guidance_scale` (autoguidance, :112-117), `score_scaling` (`_scale_score`, :7-40,
+    :119) and `weight_window_fn` as in the reference."""
     if num_steps is not None:
         scheduler.set_timesteps(num_steps)
     steps = len(scheduler.timesteps)
@@ -434,6 +469,7 @@ def sample_decoder_diffusion_tiled(model, scheduler, cond_img, noise, tile_size=
     b, c, h, w = noise.shape
     cond_img = _cond_tiles(cond_img, h, w, dev)
     T, h_starts, w_starts, tile_idx = _tile_geometry(h, w, tile_size, tile_stride, min(h, w))
+    window = _weight_window(weight_window_fn, T, dev)
     outs = []
     jobs = [(i0, j0) for i0 in h_starts for j0 in w_starts]
     per = max(1, max_batch // b)
@@ -441,8 +477,9 @@ def sample_decoder_diffusion_tiled(model, scheduler, cond_img, noise, tile_size=
         chunk = jobs[a:a + per]
         x = torch.cat([noise[:, :, i0:i0 + T, j0:j0 + T] for i0, j0 in chunk]).contiguous()       # tile-major, batch-minor
         ci = torch.cat([cond_img[:, :, i0:i0 + T, j0:j0 + T] for i0, j0 in chunk]).contiguous()
-        outs.append(sample_tiles_edm(model, scheduler, x, None, steps, cond_img=ci))
-    return _blend_batch(eng, torch.cat(outs), b, len(jobs), tile_idx, h_starts, w_starts, T, h, w, 1.0)
+        outs.append(sample_tiles_edm(model, scheduler, x, None, steps, cond_img=ci, guide_model=guidance_model, guidance_scale=guidance_scale,
+                                     score_scaling=score_scaling))
+    return _blend_batch(eng, torch.cat(outs), b, len(jobs), tile_idx, h_starts, w_starts, T, h, w, 1.0, window=window)
 
 
 @torch.no_grad()
@@ -450,8 +487,6 @@ def sample_decoder_consistency_tiled(model, scheduler, cond_img, noise, tile_siz
                                      max_batch=64):
     """sample_diffusion_decoder.py:129-211: n-step trig-flow consistency sampling of a decoder model per tile (every step re-noises with the
     SAME tile noise), blended, divided by sigma_data."""
-    if weight_window_fn is not None:
-        raise NotImplementedError("custom weight windows")
     eng, dev = model.engine, model.device
     noise = torch.as_tensor(noise).to(device=dev, dtype=torch.float32)
     b, c, h, w = noise.shape
@@ -467,6 +502,7 @@ def sample_decoder_consistency_tiled(model, scheduler, cond_img, noise, tile_siz
     else:
         extra = [float(torch.tensor(float(intermediate_t), dtype=torch.float32))]
     T, h_starts, w_starts, tile_idx = _tile_geometry(h, w, tile_size, tile_stride, min(h, w))
+    window = _weight_window(weight_window_fn, T, dev)
     jobs = [(i0, j0) for i0 in h_starts for j0 in w_starts]
     per = max(1, max_batch // b)
     outs = []
@@ -478,7 +514,7 @@ def sample_decoder_consistency_tiled(model, scheduler, cond_img, noise, tile_siz
         for t in [init_t] + extra:
             sample = consistency_step(model, t, sd, sample, z, cond=None, cond_img=ci)
         outs.append(sample)
-    return _blend_batch(eng, torch.cat(outs), b, len(jobs), tile_idx, h_starts, w_starts, T, h, w, 1.0 / sd)
+    return _blend_batch(eng, torch.cat(outs), b, len(jobs), tile_idx, h_starts, w_starts, T, h, w, 1.0 / sd, window=window)
 
 
 @torch.no_grad()
@@ -490,8 +526,6 @@ def sample_coarse_tiled(model, scheduler, cond_img, cond_snr, *, steps=15, tile_
     The reference draws both noises from torch's generators (torch.randn_like / torch.randn), which nothing else can reproduce: pass
     `cond_noise` (b, C_cond, h, w) and `init_noise` (list of (b, C_out, T, T), one per tile in row-major tile order) to pin them, otherwise
     they come from the portable stream seeded `noise_seed` (+1 + tile index for the tiles)."""
-    if weight_window_fn is not None:
-        raise NotImplementedError("custom weight windows")
     eng, dev = model.engine, model.device
     cond_img = torch.as_tensor(cond_img).to(device=dev, dtype=torch.float32)
     assert cond_img.ndim == 4, "cond_img must be [B, C, H, W]"
@@ -499,6 +533,7 @@ def sample_coarse_tiled(model, scheduler, cond_img, cond_snr, *, steps=15, tile_
     T, h_starts, w_starts, tile_idx = _tile_geometry(h, w, tile_size, tile_stride, w)
     if h < T or w < T:   # the reference sizes each tile from its cond slice (sample_coarse.py:88-92); this sampler draws square T x T tiles
         raise ValueError(f"sample_coarse_tiled: the conditioning image ({h} x {w}) is smaller than the tile ({T} x {T}); pass tile_size <= min(h, w)")
+    window = _weight_window(weight_window_fn, T, dev)
     c_out = int(model.config["out_channels"])
     snr = torch.as_tensor(cond_snr, dtype=torch.float32)
     t_cond = torch.atan(snr)
@@ -526,4 +561,4 @@ def sample_coarse_tiled(model, scheduler, cond_img, cond_snr, *, steps=15, tile_
         cond = model.cond_rows([v if v.numel() == 1 else v.repeat(len(chunk)) for v in cond_inputs], n, dev)   # tile-major, batch-minor rows
         sample_tiles_edm(model, scheduler, x, cond, int(steps), cond_img=ci)
         outs.append(x)
-    return _blend_batch(eng, torch.cat(outs), b, len(jobs), tile_idx, h_starts, w_starts, T, h, w, 1.0 / sd)
+    return _blend_batch(eng, torch.cat(outs), b, len(jobs), tile_idx, h_starts, w_starts, T, h, w, 1.0 / sd, window=window)
