@@ -342,6 +342,54 @@ __device__ __forceinline__ void epi_unit8(int epi, bool has_res, float clip, boo
     }
 }
 
+// epi_unit8 for a lane that already owns 8 CONSECUTIVE couts of one pixel (conv_glds_wide16.hip: rows 4g .. 4g + 3 of two 16x16 blocks whose MFMA rows
+// are mapped to couts c .. c+3 (va) and c+4 .. c+7 (vb)): the same transforms and roundings element by element, no lane exchange -- rw, o and o2 are the
+// lane's own 16-byte runs.  ss adds the 8 squares in epi_unit8's pairwise order; the caller adds the four lane groups of a 32-cout plane.
+template <typename T>
+__device__ __forceinline__ void epi_unit8n(int epi, bool has_res, float clip, bool want_ss, bool want_o2, f32x4 va, f32x4 vb, f32x4 ca, f32x4 cb, u32x4 rw,
+                                           float rs, SiluK k_o2, u32x4& o, u32x4& o2, float& ss) {
+    typedef typename Half<T>::x4 hx4;
+    f32x2 v[4] = {{va[0], va[1]}, {va[2], va[3]}, {vb[0], vb[1]}, {vb[2], vb[3]}};
+    if (epi == EPI_EMB_SILU) {
+        const f32x2 c[4] = {{ca[0], ca[1]}, {ca[2], ca[3]}, {cb[0], cb[1]}, {cb[2], cb[3]}};
+        const SiluK k = silu_k(1.f);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = silu_k2(v[q] * c[q], k);
+    } else if (epi == EPI_RESIDUAL) {
+        if (has_res) {
+            const hx4 ra = __builtin_bit_cast(hx4, u32x2{rw[0], rw[1]}), rb = __builtin_bit_cast(hx4, u32x2{rw[2], rw[3]});
+            const f32x2 r[4] = {{(float)ra[0], (float)ra[1]}, {(float)ra[2], (float)ra[3]}, {(float)rb[0], (float)rb[1]}, {(float)rb[2], (float)rb[3]}};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = v[q] + rs * r[q];
+        }
+        if (clip > 0.f) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = f32x2{__builtin_amdgcn_fmed3f(v[q].x, -clip, clip), __builtin_amdgcn_fmed3f(v[q].y, -clip, clip)};
+        }
+    }
+    const hx4 ha = {(T)v[0].x, (T)v[0].y, (T)v[1].x, (T)v[1].y};
+    const hx4 hb = {(T)v[2].x, (T)v[2].y, (T)v[3].x, (T)v[3].y};
+    const f32x2 f[4] = {{(float)ha[0], (float)ha[1]}, {(float)ha[2], (float)ha[3]}, {(float)hb[0], (float)hb[1]}, {(float)hb[2], (float)hb[3]}};
+    if (want_ss) {
+        f32x2 s2 = f[0] * f[0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) s2 = f[q] * f[q] + s2;
+        ss += s2.x + s2.y;
+    }
+    {
+        const u32x2 pa = __builtin_bit_cast(u32x2, ha), pb = __builtin_bit_cast(u32x2, hb);
+        o = u32x4{pa[0], pa[1], pb[0], pb[1]};
+    }
+    if (want_o2) {
+        f32x2 g[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = silu_k2(f[q], k_o2);
+        const hx4 ga = {(T)g[0].x, (T)g[0].y, (T)g[1].x, (T)g[1].y}, gb = {(T)g[2].x, (T)g[2].y, (T)g[3].x, (T)g[3].y};
+        const u32x2 qa = __builtin_bit_cast(u32x2, ga), qb = __builtin_bit_cast(u32x2, gb);
+        o2 = u32x4{qa[0], qa[1], qb[0], qb[1]};
+    }
+}
+
 // Pixel owned by lane (l31) of the 32-pixel MFMA fragment that starts at tile-linear pixel q0 (a multiple of 32).
 // ds_read_b128 is serviced in four fixed 16-lane groups, {0-3,12-15,20-27} and {4-11,16-19,28-31} for the lower half-wave (guide
 // §LDS); with 128-byte rows swizzled by ((row >> 1) & 7) a group is conflict-free iff its 16 rows are distinct mod 16.  On a

@@ -18,6 +18,7 @@
 #include "conv_igemm.hip"
 #include "conv_glds.hip"
 #include "conv_glds_wide.hip"
+#include "conv_glds_wide16.hip"
 #include "conv_sb.hip"
 #include "conv_s16.hip"
 #include "conv_fewcout.hip"
@@ -293,6 +294,7 @@ struct Op {
     bool narrow = false;
     int bn = 64;
     int glds_variant = 0;      // 0: 8 waves x 256 pixels, 1: 4 waves x 128 pixels
+    bool wide16 = false;       // glds_variant 3, bn 96, pure 3x3: the 16x16x32-MFMA form of the wide tile (conv_glds_wide16.hip)
     int flavor = 0;            // 0: per-tap register-staged kernel (conv_igemm.hip); 2: LDS-DMA throughput kernel (conv_glds.hip);
                                // (3 was the persistent ping-pong kernel of rounds 2-4, removed in round 5); 4: small-batch kernel, K split over the waves of a workgroup (conv_sb.hip);
                                // 5: deep-level latency kernel, 64 px x 16 couts on 16x16x32 MFMAs (conv_s16.hip)
@@ -679,7 +681,7 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
     static const char* const kPlanOptions[] = {"batch_invariant", "glds", "splitk", "producer_act", "glds_min_wgs", "glds_variant", "glds_bn",
                                                "glds_splitk", "glds_splitk_max", "glds_splitk_min_groups", "splitk_target_wgs",
                                                "bn128_min_wgs", "attn_mfma", "glds_splitk_from_groups", "glds_bn64", "glds_small_max_groups", "glds_round_aware", "walk_alternate", "glds_tiny", "glds_dma1x1", "splitk_weighted",
-                                               "sb", "sb_target_wgs", "sb_mt", "sb_nt", "sb_order", "sb_max_glds_wgs", "sb_splitk", "sb_splitk_wgs", "sb_splitk_max", "s16", "s16_min_wgs", "sb_m4", "glds_wide", "glds_wide_min_wgs", "glds_wide_tail", "glds_wide_persist", "fewcout"};
+                                               "sb", "sb_target_wgs", "sb_mt", "sb_nt", "sb_order", "sb_max_glds_wgs", "sb_splitk", "sb_splitk_wgs", "sb_splitk_max", "s16", "s16_min_wgs", "sb_m4", "glds_wide", "glds_wide_min_wgs", "glds_wide_tail", "glds_wide_persist", "glds_wide_mfma16", "fewcout"};
     std::string key = std::to_string(N) + "_" + std::to_string(H) + "_" + std::to_string(W);
     for (const char* o : kPlanOptions) key += "_" + std::to_string((long long)u->eng->option(o, -7));
     if (lane) key += "_lane" + std::to_string(lane);   // a second, independent activation set of the same shape (concurrent half-batches)
@@ -854,6 +856,10 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
                         for (const SegSpec& sg : segs) if (sg.taps != 9) tail3 = true;
                         if (u->eng->option("glds_wide_persist", 0) != 0 && bnw == 64 && !tail3 && (h & 15) == 0 && (w & 15) == 0 && cw.cout == cw.cout_pad)
                             p.persist = conv_wide_persist_grid((long long)p.tiles_x * p.tiles_y * N * p.n_ntiles, 2 * std::max(1, u->eng->n_cus));
+                        // The 96-cout, pure-3x3, one-tile-per-workgroup launches -- two thirds of a grid forward's conv time -- exist a second time on the
+                        // 16x16x32 MFMA shape (conv_glds_wide16.hip: same tile and pipeline, one 32-deep step per half K-step; another fp32 summation order).
+                        // Option "glds_wide_mfma16": 0 the 32x32x16 kernel everywhere, 1 the 16x16x32 kernel for these launches (profiles/wide_mfma16_ab.txt).
+                        op.wide16 = u->eng->option("glds_wide_mfma16", 1) != 0 && bnw == 96 && !tail3 && p.persist == 0;
                     }
                 }
                 // Small-batch flavour (conv_sb.hip, round 4) wherever the throughput tiles do not fill the chip (workgroups x 2 <= CU slots: the
@@ -1222,7 +1228,7 @@ static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = null
         hipError_t e = op.flavor == 6 ? launch_conv_fewcout(p, u->dt, st)   // with the solver step fused too: the same sums as the plain launch, then epilogue4's step
                        : op.flavor == 5 ? launch_conv_s16(p, u->dt, op.narrow, st)
                        : op.flavor == 4 ? launch_conv_sb(p, u->dt, op.narrow, op.sb_mt, op.sb_nt, st)
-                       : op.flavor == 2 ? (op.glds_variant == 3 ? launch_conv_glds_wide(p, u->dt, op.bn, st) : launch_conv_glds(p, u->dt, op.narrow, op.bn, op.glds_variant, st))
+                       : op.flavor == 2 ? (op.glds_variant == 3 ? (op.wide16 ? launch_conv_glds_wide16(p, u->dt, st) : launch_conv_glds_wide(p, u->dt, op.bn, st)) : launch_conv_glds(p, u->dt, op.narrow, op.bn, op.glds_variant, st))
                        : launch_conv(p, u->dt, op.narrow, op.bn, 0, st);
         mark(); if (prof) { ev_kind.push_back(0); char tag[160]; double gf_ = op.k_alg * 2.0 * p.N * p.H * p.W * p.Cout * 1e-9;  /* algorithmic GFLOP of this launch: REAL input channels (the 6-channel input conv is 5.4 GFLOP at batch 64, not the 58 its K padding to 64 would give) */
             /* algorithmic HBM megabytes of this launch: every source tensor once (at ITS resolution), the residual once, the outputs once, the weights once */
@@ -1233,7 +1239,7 @@ static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = null
             const double mbs_ = (mb_ + o1_) * 1e-6;   /* strict: without the optional pre-activated second output (an optimisation, not part of the layer's definition) */
             mb_ += o1_ * (p.out2 ? 2.0 : 1.0);
             mb_ *= 1e-6;
-            snprintf(tag, sizeof tag, " [%dx%d k%d f%d%s bn%d wg%d ks%d gf%.2f mb%.2f mbs%.2f]", p.H, p.W, p.kgroups, op.flavor, op.flavor == 5 ? "c16" : op.flavor == 4 ? (op.sb_mt == 4 ? "m4n1" : op.sb_mt == 2 ? (op.sb_nt == 2 ? "m2n2" : "m2n1") : (op.sb_nt == 2 ? "m1n2" : "m1n1")) : op.flavor == 2 ? (op.glds_variant == 3 ? (p.persist > 0 ? "wp" : "w") : op.glds_variant == 2 ? "t" : op.glds_variant ? "s" : "b") : "", op.bn, p.n_ntiles * p.tiles_x * p.tiles_y * p.img_groups, p.ksplit, gf_, mb_, mbs_); ev_label.push_back(op.label + tag);
+            snprintf(tag, sizeof tag, " [%dx%d k%d f%d%s bn%d wg%d ks%d gf%.2f mb%.2f mbs%.2f%s]", p.H, p.W, p.kgroups, op.flavor, op.flavor == 5 ? "c16" : op.flavor == 4 ? (op.sb_mt == 4 ? "m4n1" : op.sb_mt == 2 ? (op.sb_nt == 2 ? "m2n2" : "m2n1") : (op.sb_nt == 2 ? "m1n2" : "m1n1")) : op.flavor == 2 ? (op.glds_variant == 3 ? (p.persist > 0 ? "wp" : "w") : op.glds_variant == 2 ? "t" : op.glds_variant ? "s" : "b") : "", op.bn, p.n_ntiles * p.tiles_x * p.tiles_y * p.img_groups, p.ksplit, gf_, mb_, mbs_, (op.flavor == 2 && op.glds_variant == 3 && op.wide16) ? " x16" : ""); ev_label.push_back(op.label + tag);   /* x16: conv_glds_wide16.hip; the flavour tag stays f2w */
             ev_flop.push_back(op.flavor == 2 ? 2.0 * p.N * p.H * p.W * (double)p.Cout * op.k_alg : 0.0); }   // the LDS-DMA family alone (bench.py's roofline kernel); small-batch launches are told apart by their f4 label
         if (e != hipSuccess) return fail(TD_ERR_HIP, "conv launch " + op.label + ": " + hipGetErrorString(e));
     }
@@ -1304,7 +1310,7 @@ static const char* const kKnownOptions[] = {
     "plan_cache_mb", "plan_cache_max", "grid_fused",
     // plan builder (speed only, or test hooks that force a tile shape; all part of the plan-cache key)
     "attn_mfma", "bn128_min_wgs", "glds", "glds_bn", "glds_bn64", "glds_dma1x1", "glds_min_wgs", "glds_round_aware", "glds_small_max_groups",
-    "glds_splitk", "glds_splitk_from_groups", "glds_splitk_max", "glds_splitk_min_groups", "glds_tiny", "glds_variant", "glds_wide", "glds_wide_min_wgs", "glds_wide_tail", "glds_wide_persist", "fewcout",
+    "glds_splitk", "glds_splitk_from_groups", "glds_splitk_max", "glds_splitk_min_groups", "glds_tiny", "glds_variant", "glds_wide", "glds_wide_min_wgs", "glds_wide_tail", "glds_wide_persist", "glds_wide_mfma16", "fewcout",
     "producer_act", "s16", "s16_min_wgs", "sb", "sb_m4", "sb_max_glds_wgs", "sb_mt", "sb_nt", "sb_order", "sb_splitk", "sb_splitk_max", "sb_splitk_wgs", "sb_target_wgs", "splitk",
     "splitk_target_wgs", "splitk_weighted", "walk_alternate"};
 int td_engine_set_option(td_engine* e, const char* key, int64_t value) {

@@ -17,12 +17,14 @@ namespace td {
 hipError_t launch_conv(const ConvParams& p, int dtype, bool narrow, int bn, int ksplit_variant, hipStream_t st);
 hipError_t launch_conv_glds(const ConvParams& p, int dtype, bool narrow, int bn, int variant, hipStream_t st);
 hipError_t launch_conv_glds_wide(const ConvParams& p, int dtype, int bn, hipStream_t st);
+hipError_t launch_conv_glds_wide16(const ConvParams& p, int dtype, hipStream_t st);
 extern int g_bench_extra_lds;
 }
 #else
 #include "conv_igemm.hip"
 #include "conv_glds.hip"
 #include "conv_glds_wide.hip"
+#include "conv_glds_wide16.hip"
 #endif
 using namespace td;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
@@ -67,7 +69,7 @@ int main(int argc, char** argv) {
         p.nseg = 2; p.seg[1].src = x2; p.seg[1].C = Cin2; p.seg[1].cstride = Cin2; p.seg[1].Hs = H; p.seg[1].Ws = W; p.seg[1].taps = taps2; p.seg[1].xform = 0; p.seg[1].scale = 1.f;
     }
     p.dma1x1 = getenv("TD_DMA1X1") ? atoi(getenv("TD_DMA1X1")) : 1;
-    bool narrow = W < 16; int TW = narrow ? 8 : 16, NIMG = narrow ? ((flavor == 2 || flavor == 4) ? 4 : 2) : 1; const bool pers = flavor == 10; if (pers) flavor = 9;   /* 10 = the wide tile's persistent tile loop (p.persist workgroups; TD_PERSIST=G overrides 2 x 256 slots' rule) */ int TH = flavor == 8 ? 4 : ((flavor == 2 || flavor == 4 || flavor == 9) && !narrow) ? 16 : 8;  // flavor 8 = conv_glds variant 2 (tiny tile); 9 = conv_glds_wide.hip (256 px x bn, 4 waves, two workgroups per CU)
+    bool narrow = W < 16; int TW = narrow ? 8 : 16, NIMG = narrow ? ((flavor == 2 || flavor == 4) ? 4 : 2) : 1; const bool pers = flavor == 10, w16 = flavor == 11; if (pers || w16) flavor = 9;   /* 11 = conv_glds_wide16.hip, the 96-cout wide tile on the 16x16x32 MFMA shape (bn 96, pure 3x3); timed, checked and traced like 9 */   /* 10 = the wide tile's persistent tile loop (p.persist workgroups; TD_PERSIST=G overrides 2 x 256 slots' rule) */ int TH = flavor == 8 ? 4 : ((flavor == 2 || flavor == 4 || flavor == 9) && !narrow) ? 16 : 8;  // flavor 8 = conv_glds variant 2 (tiny tile); 9 = conv_glds_wide.hip (256 px x bn, 4 waves, two workgroups per CU)
     p.tiles_x = (W + TW - 1) / TW; p.tiles_y = (H + TH - 1) / TH; p.img_groups = (N + NIMG - 1) / NIMG; p.n_ntiles = Cout / bn;
     p.epi = epi; p.out = out; p.out_cstride = Cout;
     if (pers) { const long long tiles = (long long)p.n_ntiles * p.tiles_x * p.tiles_y * p.img_groups, slots = 512, rounds = (tiles + slots - 1) / slots; long long g = (tiles + rounds - 1) / rounds; if ((tiles & 7) == 0) g = (g + 7) & ~7LL;
@@ -84,7 +86,7 @@ int main(int argc, char** argv) {
     if (getenv("TD_EXTRA_LDS")) g_bench_extra_lds = atoi(getenv("TD_EXTRA_LDS"));
     hipStream_t st; CK(hipStreamCreate(&st));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    auto L = [&](const ConvParams& q) { return flavor == 9 ? launch_conv_glds_wide(q, 1, bn, st) : flavor == 8 ? launch_conv_glds(q, 1, narrow, bn, 2, st) : flavor >= 2 ? launch_conv_glds(q, 1, narrow, bn, flavor - 2, st) : launch_conv(q, 1, narrow, bn, flavor, st); };
+    auto L = [&](const ConvParams& q) { return w16 ? launch_conv_glds_wide16(q, 1, st) : flavor == 9 ? launch_conv_glds_wide(q, 1, bn, st) : flavor == 8 ? launch_conv_glds(q, 1, narrow, bn, 2, st) : flavor >= 2 ? launch_conv_glds(q, 1, narrow, bn, flavor - 2, st) : launch_conv(q, 1, narrow, bn, flavor, st); };
     for (int i = 0; i < 4; ++i) CK(L((chain && (i & 1)) ? p2 : p));
     CK(hipStreamSynchronize(st));
     const int reps = 20;
@@ -111,7 +113,7 @@ int main(int argc, char** argv) {
             fclose(fp); }
     }
     double flop = 2.0 * M * Cout * ((double)Cin * taps + (double)Cin2 * taps2);
-    printf("N%d %dx%d Cin%d Cout%d taps%d xform%d bn%d ks%d fl%d epi%d stg%d ch%d : %.1f us  %.1f TFLOP/s (%.1f%% of 2500)  wgs=%d%s\n", N, H, W, Cin, Cout, taps, xform, bn, ksplit, pers ? 10 : flavor, epi, stagger, chain, ms * 1e3,
+    printf("N%d %dx%d Cin%d Cout%d taps%d xform%d bn%d ks%d fl%d epi%d stg%d ch%d : %.1f us  %.1f TFLOP/s (%.1f%% of 2500)  wgs=%d%s\n", N, H, W, Cin, Cout, taps, xform, bn, ksplit, pers ? 10 : w16 ? 11 : flavor, epi, stagger, chain, ms * 1e3,
            flop / ms / 1e9, flop / ms / 1e9 / 25.0, p.n_ntiles * p.tiles_x * p.tiles_y * p.img_groups * ksplit, pers ? (" persistent on " + std::to_string(p.persist)).c_str() : "");
     if (pers && !getenv("TD_NO_CMP")) {   // the persistent tile loop against one tile per workgroup: same K order -> out, second output and sum-of-squares planes bit for bit
         std::vector<uint16_t> o[2], o2[2]; std::vector<float> ss[2];
