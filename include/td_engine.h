@@ -333,4 +333,7 @@ int td_perlin_map(td_engine* e, int rows, int cols, int i1, int j1, int seed, fl
 #ifdef __cplusplus
 }
 #endif
+/* ---- autoencoder: the td_ae_* entry points of this library (EDMAutoencoder, terrain_diffusion/models/edm_autoencoder.py) are declared in a header of
+ * their own, which every includer of this one gets */
+#include "td_ae.h"
 #endif

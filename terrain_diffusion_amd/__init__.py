@@ -7,6 +7,7 @@ fallback — importing is cheap, the first call that needs the engine raises if 
 """
 from ._lib import TdError, LIB_PATH, EXPORTS  # noqa: F401
 from .unet import EDMUnet2D  # noqa: F401
+from .autoencoder import EDMAutoencoder  # noqa: F401
 from .scheduler import EDMDPMSolverMultistepScheduler  # noqa: F401
 from .sampling import sample_base_diffusion, sample_base_consistency, sample_independent_tiles, _tile_starts, _linear_weight_window, _process_cond_img  # noqa: F401
 from .sampling import sample_decoder_diffusion_tiled, sample_decoder_consistency_tiled, sample_coarse_tiled  # noqa: F401

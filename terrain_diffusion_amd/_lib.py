@@ -51,6 +51,14 @@ class UnetConfig(C.Structure):
                 ("cond_type", C.c_int32 * 8), ("cond_dims", C.c_int32 * 8), ("cond_weights", C.c_float * 8)]
 
 
+class AeConfig(C.Structure):
+    """td_ae_config (include/td_ae.h): the EDMAutoencoder constructor arguments that shape its two graphs"""
+    _fields_ = [("image_size", C.c_int32), ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("model_channels", C.c_int32), ("n_levels", C.c_int32),
+                ("channel_mults", C.c_int32 * 8), ("layers_per_block", C.c_int32 * 8), ("layers_per_block_decoder", C.c_int32 * 8),
+                ("n_attn_resolutions", C.c_int32), ("attn_resolutions", C.c_int32 * 8), ("midblock_attention", C.c_int32), ("latent_channels", C.c_int32),
+                ("n_direct_skips", C.c_int32), ("direct_skips", C.c_int32 * 8)]
+
+
 _P = C.c_void_p
 
 
@@ -124,3 +132,21 @@ EXPORTS = tuple(_SIGS)
 
 _LIB = Library("libtd_engine.so", _SIGS, "td_last_error", "td_engine")
 LIB_PATH, lib, check = _LIB.path, _LIB.lib, _LIB.check
+
+# the autoencoder entry points of the same library, declared in include/td_ae.h (EXPORTS stays the list of include/td_engine.h's own declarations)
+_AE_SIGS = {
+    "td_last_error": (C.c_char_p, []),
+    "td_ae_create": (C.c_int, [_P, C.POINTER(AeConfig), C.c_int, C.POINTER(_P)]),
+    "td_ae_destroy": (None, [_P]),
+    "td_ae_num_params": (C.c_int, [_P]),
+    "td_ae_param_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int64 * 4)]),
+    "td_ae_set_param": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "td_ae_set_prefolded": (C.c_int, [_P, C.c_int]),
+    "td_ae_finalize": (C.c_int, [_P]),
+    "td_ae_preencode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_int, _P, _P, _P]),
+    "td_ae_postencode": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "td_ae_decode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, _P]),
+}
+AE_EXPORTS = tuple(k for k in _AE_SIGS if k.startswith("td_ae_"))
+_AE_LIB = Library("libtd_engine.so", _AE_SIGS, "td_last_error", "td_engine")
+ae_lib, ae_check = _AE_LIB.lib, _AE_LIB.check

@@ -25,6 +25,7 @@
 #include "small_kernels.hip"
 #include "compose_kernels.hip"
 #include "attn_mfma.hip"
+#include "ae_kernels.hip"
 
 using namespace td;
 
@@ -341,6 +342,13 @@ struct Plan {
 struct td_unet {
     td_engine* eng = nullptr;
     td_unet_config cfg;
+    // Graph kind.  0: the EDMUnet2D (encoder + skip-concat decoder, modulated by an embedding).  The two stacks of the EDMAutoencoder have no embedding
+    // (emb_channels = 0: a block's epilogue is mp_silu(y), unet_block.py:133-134 -- run as EPI_EMB_SILU on a modulation row of 1.0f, which is exact):
+    // 1: encoder only, out_conv on the bottleneck (edm_unet.py:107-139 with encode_only); 2: skip-less decoder behind a 1x1 decoder_conv (edm_autoencoder.py:86-103)
+    int kind = 0;
+    int lpb_dec[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // kind 2: layers_per_block_decoder
+    std::string out_label = "out_conv", out_gain_name = "out_gain";   // kind 1: "encoder.out_conv" / "encoder.out_gain"
+    Buf d_ones;                // kinds 1 and 2: the all-ones modulation row every block reads (cvec stride 0)
     bool bf16 = false;         // 16-bit storage (bf16 OR fp16): 64-channel K chunks, LDS-DMA / small-batch conv flavours available
     int dt = TD_DTYPE_F32;     // TD_DTYPE_*
     int chunk = 32;            // channels per 128-byte K chunk
@@ -456,6 +464,70 @@ static int build_blocks(td_unet* u) {
     return TD_OK;
 }
 
+// The two stacks of the EDMAutoencoder as Block lists (edm_autoencoder.py:66-103; names are the reference's state-dict prefixes).  u->cfg carries the
+// stack's own channels: kind 1 in_channels -> 2 * latent_channels, kind 2 latent + direct channels -> out_channels.  No embedding parameters; the
+// reference's unused `emb_gain` scalars are not expected.
+static int build_blocks_ae(td_unet* u) {
+    const td_unet_config& c = u->cfg;
+    if (c.n_levels < 1 || c.n_levels > 8) return fail(TD_ERR_ARG, "n_levels out of range");
+    auto has_attn = [&](int res) { for (int i = 0; i < c.n_attn_resolutions; ++i) if (c.attn_resolutions[i] == res) return true; return false; };
+    u->emb_ch = 0; u->noise_dims = 0; u->c_total = 0;
+    int cout = c.in_channels + 1;
+    if (u->kind == 1) {   // edm_unet.py:107-121, encode_only
+        u->out_label = "encoder.out_conv"; u->out_gain_name = "encoder.out_gain";
+        for (int l = 0; l < c.n_levels; ++l) {
+            int ch = c.model_channels * c.channel_mults[l], res = c.image_size >> l;
+            std::string r = "encoder.enc." + std::to_string(res) + "x" + std::to_string(res);
+            Block b;
+            if (l == 0) { b.name = r + "_conv"; b.is_conv = true; b.cin = cout; b.cout = ch; cout = ch; }
+            else { b.name = r + "_down"; b.cin = cout; b.cout = cout; b.resample = 1; }
+            u->enc.push_back(b);
+            for (int i = 0; i < c.layers_per_block[l]; ++i) {
+                Block k;
+                k.name = r + "_block" + std::to_string(i);
+                k.cin = cout; k.cout = ch; k.attn = has_attn(res); cout = ch;
+                u->enc.push_back(k);
+            }
+        }
+    } else {              // edm_autoencoder.py:87-101
+        const int c0 = c.model_channels * c.channel_mults[c.n_levels - 1];
+        add_param(u, "decoder_conv.weight", {c0, cout, 1, 1});
+        cout = c0;
+        int idx = 0;
+        auto push = [&](int cin_, int cout_, int resample, bool attn) {
+            Block k;
+            k.name = "decoder." + std::to_string(idx++);
+            k.enc = false; k.cin = cin_; k.cout = cout_; k.resample = resample; k.attn = attn;
+            u->dec.push_back(k);
+        };
+        for (int l = c.n_levels - 1; l >= 0; --l) {
+            int ch = c.model_channels * c.channel_mults[l], res = c.image_size >> l;
+            if (l == c.n_levels - 1) { push(cout, cout, 0, c.midblock_attention != 0); push(cout, cout, 0, false); }
+            else push(cout, cout, 2, false);
+            for (int i = 0; i < u->lpb_dec[l] + 1; ++i) { push(cout, ch, 0, has_attn(res)); cout = ch; }
+        }
+    }
+    u->final_c = cout;
+    auto add_block = [&](Block& b) {
+        if (b.is_conv) { add_param(u, b.name + ".weight", {b.cout, b.cin, 3, 3}); return; }
+        b.cvec_off = 0;
+        add_param(u, b.name + ".conv_res0.weight", {b.cout, b.enc ? b.cout : b.cin, 3, 3});
+        add_param(u, b.name + ".conv_res1.weight", {b.cout, b.cout, 3, 3});
+        if (b.cin != b.cout) add_param(u, b.name + ".conv_skip.weight", {b.cout, b.cin, 1, 1});
+        if (b.attn) {
+            add_param(u, b.name + ".attn_qkv.weight", {3 * b.cout, b.cout, 1, 1});
+            add_param(u, b.name + ".attn_proj.weight", {b.cout, b.cout, 1, 1});
+        }
+    };
+    for (auto& b : u->enc) add_block(b);
+    for (auto& b : u->dec) add_block(b);
+    add_param(u, u->out_label + ".weight", {c.out_channels, u->final_c, 3, 3});
+    add_param(u, u->out_gain_name, {});
+    for (auto& b : u->enc) if (!b.is_conv && (b.cout % 64 || b.cin % 64)) return fail(TD_ERR_UNSUPPORTED, "block channels must be multiples of 64: " + b.name);
+    for (auto& b : u->dec) if (b.cout % 64 || b.cin % 64) return fail(TD_ERR_UNSUPPORTED, "block channels must be multiples of 64: " + b.name);
+    return TD_OK;
+}
+
 // mp_layers.py:203-213 (eval): W / (1e-4 + ||W||_2 / sqrt(numel)) * gain / sqrt(fan_in)
 static void fold(const Param& p, float gain, std::vector<float>& out, bool prefolded) {
     const int64_t n = p.numel();
@@ -553,10 +625,19 @@ static int finalize(td_unet* u) {
         return &v;
     };
     auto pad = [&](int c) { return (c + chunk - 1) / chunk * chunk; };
-    const float out_gain = P(u, "out_gain").data[0];
+    const float out_gain = P(u, u->out_gain_name).data[0];
     int rc;
+    if (u->kind != 0) {   // no embedding: one row of ones serves every block and every image (+ slack for the epilogues' 16-byte row reads)
+        int max_cout = 64;
+        for (auto& b : u->enc) max_cout = std::max(max_cout, b.cout);
+        for (auto& b : u->dec) max_cout = std::max(max_cout, b.cout);
+        std::vector<float> ones((size_t)max_cout + 256, 1.f);
+        u->d_ones.reset(new DevBuf());
+        HIP_TRY(u->d_ones->alloc(ones.size() * 4, false));
+        HIP_TRY(hipMemcpy(u->d_ones->p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice));
+    }
     // embedding path (fp32 on device)
-    {
+    if (u->kind == 0) {
         auto up = [&](Buf& b, const std::vector<float>& v) -> int {
             b.reset(new DevBuf());
             HIP_TRY(b->alloc(v.size() * 4, false));
@@ -654,9 +735,13 @@ static int finalize(td_unet* u) {
         }
         return TD_OK;
     };
+    if (u->kind == 2) {   // decoder_conv: 1x1 over latent + direct + ones channels (edm_autoencoder.py:89,137-138)
+        const int cin = u->cfg.in_channels + 1, c0 = u->dec.front().cin;
+        if ((rc = mk("decoder_conv", c0, {seg("decoder_conv.weight", 1.f, cin, 0, cin, 1, 1.f)}))) return rc;
+    }
     for (auto& b : u->enc) if ((rc = do_block(b))) return rc;
     for (auto& b : u->dec) if ((rc = do_block(b))) return rc;
-    if ((rc = mk("out_conv", u->cfg.out_channels, {seg("out_conv.weight", out_gain, u->final_c, 0, u->final_c, 9, 1.f)}))) return rc;
+    if ((rc = mk(u->out_label, u->cfg.out_channels, {seg(u->out_label + ".weight", out_gain, u->final_c, 0, u->final_c, 9, 1.f)}))) return rc;
     for (auto& p : u->params) { p.data.clear(); p.data.shrink_to_fit(); }
     u->folded.clear();
     HIP_TRY(hipDeviceSynchronize());
@@ -689,7 +774,8 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
     if (it != u->plans.end()) { it->second->last_use = ++u->use_clock; *out = it->second.get(); return TD_OK; }
     if (N < 1 || N > 1023 || H > 1023 || W > 1023) return fail(TD_ERR_ARG, "batch/size out of range");
     const int down = 1 << (u->cfg.n_levels - 1);
-    if (H % down || W % down) return fail(TD_ERR_ARG, "H and W must be divisible by 2^(levels-1)");
+    if (u->kind != 2 && (H % down || W % down)) return fail(TD_ERR_ARG, "H and W must be divisible by 2^(levels-1)");
+    if (u->kind == 2 && (H * down > 1023 || W * down > 1023)) return fail(TD_ERR_ARG, "batch/size out of range");   // (the decoder's input is the latent: its maps grow)
     // plan cache: least-recently-used plans are dropped once the cached plans exceed the byte budget (each owns a full activation set;
     // InfiniteTensor batches vary in size, so an unbounded cache would pin one activation set per batch size ever seen)
     {
@@ -990,7 +1076,9 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
     // with option attn_mfma = 0 -- runs the scalar attn_kernel (small_kernels.hip), whose LDS tiles hold 64 tokens: more is refused here, before anything is launched
     const bool attn_on_mfma = u->dt == TD_DTYPE_BF16 && u->eng->option("attn_mfma", 1) != 0;
     auto attn_fits = [&](int tokens, const std::string& name) -> int {
-        if (tokens > 64 && !attn_on_mfma)
+        // (the autoencoder graphs run such a block on the one-wave-per-query kernel of ae_kernels.hip instead: run_unet)
+        if (tokens > 65535) return fail(TD_ERR_UNSUPPORTED, "attention over more than 65535 tokens: " + name);
+        if (tokens > 64 && !attn_on_mfma && u->kind == 0)
             return fail(TD_ERR_UNSUPPORTED, "attention over more than 64 tokens needs bf16 mode with option attn_mfma = 1 (MFMA kernel; the scalar kernel holds 64): " + name);
         return TD_OK;
     };
@@ -1014,6 +1102,11 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
     std::vector<Tensor> skips;
     Tensor cur = xin;
     int h = H, w = W;
+    if (u->kind == 2) {
+        Tensor o;
+        if ((rc = conv("decoder_conv", {{&cur, chunk, 1, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, false, &o))) return rc;
+        cur = o;
+    }
     for (size_t bi = 0; bi < u->enc.size(); ++bi) {
         const Block& b = u->enc[bi];
         // does the consumer of this block's output pixel-normalise it directly (enc block without skip conv)?
@@ -1082,7 +1175,7 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         cur = o;
     }
     Tensor Ft;
-    if ((rc = conv("out_conv", {{&cur, u->final_c, 9, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, true, &Ft))) return rc;
+    if ((rc = conv(u->out_label, {{&cur, u->final_c, 9, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, true, &Ft))) return rc;
     pl.F = (float*)Ft.ptr;
     // Producer-side activation: a segment that takes mp_silu(scale * x) of a whole conv output (decoder blocks: the running tensor
     // and the skip tensor of the concatenation) reads a second copy that the PRODUCER's epilogue writes already activated, instead of
@@ -1116,7 +1209,7 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         pl.partial = (float*)pp;
         for (auto& op : pl.ops) if (op.kind == Op::CONV) op.p.partial = pl.partial;
     }
-    const size_t xbytes = (size_t)N * std::max(u->cfg.in_channels, u->cfg.out_channels) * H * W * 4;
+    const size_t xbytes = u->kind != 0 ? 16 : (size_t)N * std::max(u->cfg.in_channels, u->cfg.out_channels) * H * W * 4;   // (no sampler runs on the autoencoder's stacks)
     pl.x.reset(new DevBuf()); pl.m1.reset(new DevBuf()); pl.m2.reset(new DevBuf()); pl.xt.reset(new DevBuf()); pl.cond.reset(new DevBuf());
     HIP_TRY(pl.x->alloc(xbytes)); HIP_TRY(pl.m1->alloc(xbytes)); HIP_TRY(pl.m2->alloc(xbytes)); HIP_TRY(pl.xt->alloc(xbytes));
     HIP_TRY(pl.cond->alloc((size_t)N * std::max(1, u->cond_row_len) * 4));
@@ -1178,7 +1271,7 @@ static int compute_cvecs(td_unet* u, Plan& pl, const std::vector<float>& t_steps
 // `fuse` (EDM sampler): the output conv runs the DPM-Solver++ update of this step in its epilogue (EPI_DPM_STEP) instead of writing F
 static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = nullptr) {
     hipStream_t st = u->eng->stream;
-    const float* cbase = (const float*)pl.cvec->p + (size_t)step * pl.N * u->c_total;
+    const float* cbase = u->kind != 0 ? (const float*)u->d_ones->p : (const float*)pl.cvec->p + (size_t)step * pl.N * u->c_total;
     const bool prof = u->eng->option("profile", 0) != 0;
     std::vector<hipEvent_t> evs;
     std::vector<int> ev_kind;
@@ -1213,7 +1306,9 @@ static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = null
                 hipError_t ea = attn_pack_qkv64<__bf16>(qkv, 3L * op.C, pl.N, Hh, L, 0.125f, Qp, Kp, Vt, st);   // one launch for q, k and v (the generic attn_pack: td_attention)
                 if (ea == hipSuccess) ea = attn_mfma(Qp, Kp, Vt, nullptr, (__bf16*)op.att, so, pl.N, Hh, L, L, 64, st);
                 if (ea != hipSuccess) return fail(TD_ERR_HIP, std::string("attention launch: ") + hipGetErrorString(ea));
-            } else
+            } else if (op.tokens > 64)   // autoencoder graphs only (build_plan refuses it for the U-Net)
+            TD_DISPATCH_T(u, hipLaunchKernelGGL(ae_attn_wave_kernel<T_>, dim3(pl.N, op.C / 64, (op.tokens + 3) / 4), dim3(256), 0, st, (const T_*)op.qkv, (T_*)op.att, op.tokens, op.C));
+            else
             TD_DISPATCH_T(u, hipLaunchKernelGGL(attn_kernel<T_>, dim3(pl.N, op.C / 64), dim3(256), 0, st, (const T_*)op.qkv, (T_*)op.att, op.tokens, op.C));
             mark(); if (prof) { ev_kind.push_back(1); ev_label.push_back(op.label); ev_flop.push_back(0.0); }
             HIP_TRY(hipGetLastError());
@@ -2281,6 +2376,214 @@ int td_attention(td_engine* e, const float* q, const float* k, const float* v, i
     if ((rc = out_finish(e, os))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return TD_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================ EDMAutoencoder
+// Two graphs on the U-Net's block machinery (td_unet::kind 1 and 2), one handle, one parameter list under the reference's state-dict names.
+struct td_ae {
+    td_engine* eng = nullptr;
+    td_ae_config cfg;
+    std::unique_ptr<td_unet> enc, dec;
+    AeDirect dir;
+    int L = 0, D = 0, sdown = 1;
+};
+
+static td_unet* ae_owner(td_ae* a, const char* name) {
+    if (a->enc->pindex.count(name)) return a->enc.get();
+    if (a->dec->pindex.count(name)) return a->dec.get();
+    return nullptr;
+}
+// names the reference's state dict carries and inference never reads (unet_block.py:72 with emb_channels = 0; edm_autoencoder.py:105; edm_unet.py:142-143)
+static bool ae_ignored(const std::string& n) {
+    const std::string eg = ".emb_gain";
+    return (n.size() > eg.size() && n.compare(n.size() - eg.size(), eg.size(), eg) == 0) || n == "logvar" || n.rfind("encoder.logvar_", 0) == 0;
+}
+
+// option "profile": HIP events around the kernels of ae_kernels.hip, accumulated with the U-Net's non-conv kernels (td_engine_profile_read: other_ms) under
+// their own labels; as in run_unet the read-out waits for the stream, so a profiled call is not enqueue-only
+struct AeProf {
+    td_engine* e;
+    bool on;
+    std::vector<hipEvent_t> evs;
+    std::vector<std::string> labels;
+    explicit AeProf(td_engine* e_) : e(e_), on(e_->option("profile", 0) != 0) {}
+    void mark(const char* label) {   // call before and after a launch; the label of the first call counts
+        if (!on) return;
+        hipEvent_t ev;
+        if (hipEventCreate(&ev) != hipSuccess) return;
+        (void)hipEventRecord(ev, e->stream);
+        evs.push_back(ev);
+        if (evs.size() & 1) labels.push_back(label);
+    }
+    ~AeProf() {
+        if (evs.empty()) return;
+        (void)hipStreamSynchronize(e->stream);
+        for (size_t i = 0; i + 1 < evs.size(); i += 2) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
+            auto& po = e->prof_ops[labels[i / 2]]; po.first += ms; po.second++;
+            e->prof_other_ms += ms; e->prof_other_launches++;
+        }
+        for (auto ev : evs) (void)hipEventDestroy(ev);
+    }
+};
+
+extern "C" {
+
+int td_ae_create(td_engine* e, const td_ae_config* cfg, int dtype, td_ae** out) {
+    if (!e || !cfg || !out) return fail(TD_ERR_ARG, "null argument");
+    if (dtype != TD_DTYPE_F32 && dtype != TD_DTYPE_BF16 && dtype != TD_DTYPE_F16) return fail(TD_ERR_ARG, "dtype");
+    const td_ae_config& c = *cfg;
+    const int L = c.latent_channels, D = c.n_direct_skips;
+    if (c.n_levels < 1 || c.n_levels > 8) return fail(TD_ERR_ARG, "n_levels out of range");
+    if (L < 1) return fail(TD_ERR_ARG, "latent_channels must be given");
+    if (L > 4) return fail(TD_ERR_UNSUPPORTED, "latent_channels must be <= 4 (the encoder's output conv writes 2 * latent_channels <= 8 channels)");
+    if (D < 0 || D > 8 || L + D + 1 > 32) return fail(TD_ERR_UNSUPPORTED, "latent_channels + len(direct_skips) + 1 must fit one K chunk (<=32), at most 8 direct skips");
+    if (c.in_channels < 1 || c.in_channels + 1 > 32) return fail(TD_ERR_UNSUPPORTED, "in_channels+1 must fit one K chunk (<=32)");
+    if (c.out_channels < 1 || c.out_channels > 8) return fail(TD_ERR_UNSUPPORTED, "out_channels must be <= 8");
+    for (int d = 0; d < D; ++d)
+        if (c.direct_skips[d] < 0 || c.direct_skips[d] >= c.in_channels || c.direct_skips[d] >= c.out_channels) return fail(TD_ERR_ARG, "direct_skips entry outside the input / output channels");
+    std::unique_ptr<td_ae> a(new td_ae());
+    a->eng = e; a->cfg = c; a->L = L; a->D = D; a->sdown = 1 << (c.n_levels - 1);
+    memset(&a->dir, 0, sizeof a->dir);
+    a->dir.n = D;
+    for (int d = 0; d < D; ++d) a->dir.ch[d] = c.direct_skips[d];
+    for (int kind = 1; kind <= 2; ++kind) {
+        std::unique_ptr<td_unet> u(new td_unet());
+        u->eng = e; u->dt = dtype; u->bf16 = dtype != TD_DTYPE_F32; u->chunk = u->bf16 ? 64 : 32; u->kind = kind;
+        memset(&u->cfg, 0, sizeof u->cfg);
+        u->cfg.image_size = c.image_size; u->cfg.model_channels = c.model_channels; u->cfg.n_levels = c.n_levels;
+        u->cfg.in_channels = kind == 1 ? c.in_channels : L + D;
+        u->cfg.out_channels = kind == 1 ? 2 * L : c.out_channels;
+        for (int l = 0; l < c.n_levels; ++l) { u->cfg.channel_mults[l] = c.channel_mults[l]; u->cfg.layers_per_block[l] = c.layers_per_block[l]; u->lpb_dec[l] = c.layers_per_block_decoder[l]; }
+        u->cfg.n_attn_resolutions = std::min(8, std::max(0, c.n_attn_resolutions));
+        for (int i = 0; i < u->cfg.n_attn_resolutions; ++i) u->cfg.attn_resolutions[i] = c.attn_resolutions[i];
+        u->cfg.midblock_attention = kind == 2 ? c.midblock_attention : 0;   // (the encoder has no mid block: edm_unet.py:128-129)
+        u->cfg.concat_balance = 0.5f;
+        int rc = build_blocks_ae(u.get());
+        if (rc) return rc;
+        (kind == 1 ? a->enc : a->dec) = std::move(u);
+    }
+    *out = a.release();
+    return TD_OK;
+}
+void td_ae_destroy(td_ae* a) {
+    if (!a) return;
+    DevGuard dg_(a->eng->device);
+    (void)hipStreamSynchronize(a->eng->stream);
+    delete a;
+}
+int td_ae_num_params(td_ae* a) { return (int)(a->enc->params.size() + a->dec->params.size()); }
+int td_ae_param_info(td_ae* a, int i, const char** name, int32_t* ndim, int64_t shape[4]) {
+    const int ne = (int)a->enc->params.size();
+    if (i < 0 || i >= td_ae_num_params(a)) return fail(TD_ERR_ARG, "index");
+    return i < ne ? td_unet_param_info(a->enc.get(), i, name, ndim, shape) : td_unet_param_info(a->dec.get(), i - ne, name, ndim, shape);
+}
+int td_ae_set_param(td_ae* a, const char* name, const float* host_data, int64_t numel) {
+    if (!a || !name) return fail(TD_ERR_ARG, "null argument");
+    if (ae_ignored(name)) return TD_OK;
+    td_unet* u = ae_owner(a, name);
+    if (!u) return fail(TD_ERR_ARG, std::string("unknown parameter ") + name);
+    return td_unet_set_param(u, name, host_data, numel);
+}
+int td_ae_set_prefolded(td_ae* a, int prefolded) {
+    int rc = td_unet_set_prefolded(a->enc.get(), prefolded);
+    return rc ? rc : td_unet_set_prefolded(a->dec.get(), prefolded);
+}
+int td_ae_finalize(td_ae* a) {
+    int rc = td_unet_finalize(a->enc.get());
+    return rc ? rc : td_unet_finalize(a->dec.get());
+}
+
+int td_ae_preencode(td_ae* a, int n_src, int H, int W, const float* x, float mean, float std, int dihedral, float* means, float* logvars, void* packed_f16) {
+    if (!a || !x || !means || !logvars) return fail(TD_ERR_ARG, "td_ae_preencode: null argument");
+    td_engine* e = a->eng;
+    td_unet* u = a->enc.get();
+    DevGuard dg_(e->device);
+    if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
+    if (n_src < 1 || H < 1 || W < 1) return fail(TD_ERR_ARG, "td_ae_preencode: bad geometry");
+    if (dihedral && H != W) return fail(TD_ERR_UNSUPPORTED, "td_ae_preencode: the dihedral form needs H == W");
+    const int n = dihedral ? 8 * n_src : n_src, C = a->cfg.in_channels, LD = a->L + a->D, s = a->sdown;
+    Plan* pl;
+    int rc = build_plan(u, n, H, W, &pl);   // (refuses H, W not divisible by 2^(levels-1))
+    if (rc) return rc;
+    const int h = H / s, w = W / s;
+    hipStream_t st = e->stream;
+    std::vector<Buf> hold;
+    const void* dx;
+    if ((rc = to_device(e, x, (size_t)n_src * C * H * W * 4, hold, &dx))) return rc;
+    OutStage om, ol, op;
+    const size_t lat = (size_t)n * LD * h * w;
+    if ((rc = out_device(e, means, lat * 4, hold, &om)) || (rc = out_device(e, logvars, lat * 4, hold, &ol))) return rc;
+    op.dev = nullptr; op.host = nullptr; op.bytes = 0;
+    if (packed_f16 && (rc = out_device(e, packed_f16, lat * 2 * 2, hold, &op))) return rc;
+    AeSrc src;
+    src.x = (const float*)dx; src.C = C; src.H = H; src.W = W; src.dihedral = dihedral ? 1 : 0; src.mean = mean; src.std = std;
+    AeProf prof(e);
+    prof.mark("ae_prep_input");
+    TD_DISPATCH_T(u, hipLaunchKernelGGL(ae_prep_input_kernel<T_>, grid1((size_t)n * H * W), dim3(256), 0, st, src, (T_*)pl->xin, n, u->chunk));
+    prof.mark("ae_prep_input");
+    HIP_TRY(hipGetLastError());
+    if ((rc = run_unet(u, *pl, 0))) return rc;
+    prof.mark("ae_latent_head");
+    hipLaunchKernelGGL(ae_latent_head_kernel, grid1((size_t)n * h * w), dim3(256), 0, st, (const float*)pl->F, 8, src, a->dir, n, a->L, h, w, s, (float*)om.dev, (float*)ol.dev,
+                       (_Float16*)op.dev);
+    prof.mark("ae_latent_head");
+    HIP_TRY(hipGetLastError());
+    if ((rc = out_finish(e, om)) || (rc = out_finish(e, ol))) return rc;
+    if (packed_f16 && (rc = out_finish(e, op))) return rc;
+    return end_call(e, hold, !om.host && !ol.host && !op.host && is_device_ptr(x));
+}
+
+int td_ae_postencode(td_ae* a, int64_t numel, const float* means, const float* logvars, const float* eps, float* z) {
+    if (!a || !means || !logvars || !eps || !z || numel < 1) return fail(TD_ERR_ARG, "td_ae_postencode: bad arguments");
+    td_engine* e = a->eng;
+    DevGuard dg_(e->device);
+    std::vector<Buf> hold;
+    const void *dm, *dl, *de;
+    int rc;
+    if ((rc = to_device(e, means, (size_t)numel * 4, hold, &dm)) || (rc = to_device(e, logvars, (size_t)numel * 4, hold, &dl)) || (rc = to_device(e, eps, (size_t)numel * 4, hold, &de))) return rc;
+    OutStage os;
+    if ((rc = out_device(e, z, (size_t)numel * 4, hold, &os))) return rc;
+    hipLaunchKernelGGL(ae_postencode_kernel, grid1((size_t)numel), dim3(256), 0, e->stream, (const float*)dm, (const float*)dl, (const float*)de, (float*)os.dev, (size_t)numel);
+    HIP_TRY(hipGetLastError());
+    if ((rc = out_finish(e, os))) return rc;
+    return end_call(e, hold, !os.host && is_device_ptr(means) && is_device_ptr(logvars) && is_device_ptr(eps));
+}
+
+int td_ae_decode(td_ae* a, int n, int h, int w, const float* z, float std, float mean, float* out) {
+    if (!a || !z || !out) return fail(TD_ERR_ARG, "td_ae_decode: null argument");
+    td_engine* e = a->eng;
+    td_unet* u = a->dec.get();
+    DevGuard dg_(e->device);
+    if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
+    if (n < 1 || h < 1 || w < 1) return fail(TD_ERR_ARG, "td_ae_decode: bad geometry");
+    Plan* pl;
+    int rc = build_plan(u, n, h, w, &pl);
+    if (rc) return rc;
+    const int LD = a->L + a->D, s = a->sdown, H = h * s, W = w * s, Co = a->cfg.out_channels;
+    hipStream_t st = e->stream;
+    std::vector<Buf> hold;
+    const void* dz;
+    if ((rc = to_device(e, z, (size_t)n * LD * h * w * 4, hold, &dz))) return rc;
+    OutStage os;
+    if ((rc = out_device(e, out, (size_t)n * Co * H * W * 4, hold, &os))) return rc;
+    // z + ones channel -> NHWC storage type (edm_autoencoder.py:137): the U-Net's input staging as it is
+    AeProf prof(e);
+    prof.mark("ae_decode_head");
+    TD_DISPATCH_T(u, hipLaunchKernelGGL(prep_input_kernel<T_>, grid1((size_t)n * h * w), dim3(256), 0, st, (const float*)dz, (T_*)pl->xin, n, LD, h * w, u->chunk, 1.f, LD));
+    prof.mark("ae_decode_head");
+    HIP_TRY(hipGetLastError());
+    if ((rc = run_unet(u, *pl, 0))) return rc;
+    prof.mark("ae_decode_finish");
+    hipLaunchKernelGGL(ae_decode_finish_kernel, grid1((size_t)n * H * W), dim3(256), 0, st, (const float*)pl->F, 8, (const float*)dz, a->dir, n, Co, a->L, H, W, s,
+                       (std != 1.f || mean != 0.f) ? 1 : 0, std, mean, (float*)os.dev);
+    prof.mark("ae_decode_finish");
+    HIP_TRY(hipGetLastError());
+    if ((rc = out_finish(e, os))) return rc;
+    return end_call(e, hold, !os.host && is_device_ptr(z));
 }
 
 }  // extern "C"
