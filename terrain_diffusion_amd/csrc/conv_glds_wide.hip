@@ -776,16 +776,6 @@ static hipError_t launch_glds_wide_cfg2(const ConvParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-// Number of persistent workgroups for a launch of `tiles` workgroup tiles on `slots` resident workgroup slots (2 per CU): every workgroup walks
-// ceil(tiles / slots) tiles (the last round may be short); a multiple of 8 when the launch's tile count is (XCD ranges).  0 = not worth it (one round).
-inline int conv_wide_persist_grid(long long tiles, int slots) {
-    if (tiles < 2LL * slots) return 0;
-    const long long rounds = (tiles + slots - 1) / slots;
-    long long g = (tiles + rounds - 1) / rounds;
-    if ((tiles & 7) == 0) g = (g + 7) & ~7LL;
-    return (int)std::min<long long>(g, tiles);
-}
-
 template <typename T, int BN>
 static hipError_t launch_glds_wide_cfg(const ConvParams& p, hipStream_t st) {
     bool tail = false;

@@ -13,6 +13,7 @@
 
 #include "../../include/td_engine.h"
 #include "td_device.h"
+#include "conv_select.h"
 
 // single translation unit: kernels are compiled together with the host runtime
 #include "conv_igemm.hip"
@@ -292,14 +293,7 @@ struct Tensor {
 struct Op {
     enum Kind { CONV, ATTN } kind = CONV;
     ConvParams p;
-    bool narrow = false;
-    int bn = 64;
-    int glds_variant = 0;      // 0: 8 waves x 256 pixels, 1: 4 waves x 128 pixels
-    bool wide16 = false;       // glds_variant 3, bn 96, pure 3x3: the 16x16x32-MFMA form of the wide tile (conv_glds_wide16.hip)
-    int flavor = 0;            // 0: per-tap register-staged kernel (conv_igemm.hip); 2: LDS-DMA throughput kernel (conv_glds.hip);
-                               // (3 was the persistent ping-pong kernel of rounds 2-4, removed in round 5); 4: small-batch kernel, K split over the waves of a workgroup (conv_sb.hip);
-                               // 5: deep-level latency kernel, 64 px x 16 couts on 16x16x32 MFMAs (conv_s16.hip)
-    int sb_mt = 2, sb_nt = 2;  // flavour 4: 32-pixel / 32-cout MFMA blocks per workgroup
+    ConvSel sel;               // kernel, tile and split of this op (conv_select.h)
     int cvec_off = -1;         // EPI_EMB_SILU: offset of this block's c vector
     double k_alg = 0.0;        // sum over the K-segments of (real input channels x taps): the algorithmic K of the op (profile labels, roofline FLOP)
     int out_C = 0, out_H = 0, out_W = 0;  // output tensor geometry (debug read-back)
@@ -761,14 +755,57 @@ static int new_buf(Plan& pl, size_t bytes, void** out) {
 
 struct SegSpec { const Tensor* t; int C; int taps; int resample; int xform; float scale; };
 
+// The plan options (conv_select.h: PlanOptions) with the defaults that ship.  These are the ONLY read sites of plan options: the plan builder and the
+// conv selector work on the struct, and build_plan makes the plan-cache key from its members.
+static PlanOptions read_plan_options(const td_engine* e) {
+    PlanOptions o;
+    o.batch_invariant = e->option("batch_invariant", 0);
+    o.attn_mfma = e->option("attn_mfma", 1);
+    o.bn128_min_wgs = e->option("bn128_min_wgs", 128);
+    o.glds = e->option("glds", 1);
+    o.glds_bn = e->option("glds_bn", 0);
+    o.glds_bn64 = e->option("glds_bn64", 1);
+    o.glds_dma1x1 = e->option("glds_dma1x1", 1);
+    o.glds_min_wgs = e->option("glds_min_wgs", 8);
+    o.glds_round_aware = e->option("glds_round_aware", 1);
+    o.glds_small_max_groups = e->option("glds_small_max_groups", 6);
+    o.glds_splitk = e->option("glds_splitk", 1);
+    o.glds_splitk_from_groups = e->option("glds_splitk_from_groups", 2);
+    o.glds_splitk_max = e->option("glds_splitk_max", 32);
+    o.glds_splitk_min_groups = e->option("glds_splitk_min_groups", 1);
+    o.glds_tiny = e->option("glds_tiny", 0);
+    o.glds_variant = e->option("glds_variant", -1);
+    o.glds_wide = e->option("glds_wide", 1);
+    o.glds_wide_min_wgs = e->option("glds_wide_min_wgs", 384);
+    o.glds_wide_tail = e->option("glds_wide_tail", 1);
+    o.glds_wide_persist = e->option("glds_wide_persist", 0);
+    o.glds_wide_mfma16 = e->option("glds_wide_mfma16", 1);
+    o.fewcout = e->option("fewcout", 1);
+    o.producer_act = e->option("producer_act", 1);
+    o.s16 = e->option("s16", 1);
+    o.s16_min_wgs = e->option("s16_min_wgs", 128);
+    o.sb = e->option("sb", 1);
+    o.sb_m4 = e->option("sb_m4", 0);
+    o.sb_max_glds_wgs = e->option("sb_max_glds_wgs", 1 << 30);
+    o.sb_mt = e->option("sb_mt", 0);
+    o.sb_nt = e->option("sb_nt", 0);
+    o.sb_order = e->option("sb_order", -1);
+    o.sb_splitk = e->option("sb_splitk", 1);
+    o.sb_splitk_max = e->option("sb_splitk_max", 16);
+    o.sb_splitk_wgs = e->option("sb_splitk_wgs", 224);
+    o.sb_target_wgs = e->option("sb_target_wgs", 160);
+    o.splitk = e->option("splitk", 1);
+    o.splitk_target_wgs = e->option("splitk_target_wgs", 512);
+    o.splitk_weighted = e->option("splitk_weighted", 1);
+    o.walk_alternate = e->option("walk_alternate", 1);
+    return o;
+}
+
 static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0) {
-    // every option the plan builder reads is part of the cache key (a plan built under other options must never be reused)
-    static const char* const kPlanOptions[] = {"batch_invariant", "glds", "splitk", "producer_act", "glds_min_wgs", "glds_variant", "glds_bn",
-                                               "glds_splitk", "glds_splitk_max", "glds_splitk_min_groups", "splitk_target_wgs",
-                                               "bn128_min_wgs", "attn_mfma", "glds_splitk_from_groups", "glds_bn64", "glds_small_max_groups", "glds_round_aware", "walk_alternate", "glds_tiny", "glds_dma1x1", "splitk_weighted",
-                                               "sb", "sb_target_wgs", "sb_mt", "sb_nt", "sb_order", "sb_max_glds_wgs", "sb_splitk", "sb_splitk_wgs", "sb_splitk_max", "s16", "s16_min_wgs", "sb_m4", "glds_wide", "glds_wide_min_wgs", "glds_wide_tail", "glds_wide_persist", "glds_wide_mfma16", "fewcout"};
+    // every plan option is part of the cache key, by its effective value (a plan built under other options must never be reused)
+    PlanOptions po = read_plan_options(u->eng);
     std::string key = std::to_string(N) + "_" + std::to_string(H) + "_" + std::to_string(W);
-    for (const char* o : kPlanOptions) key += "_" + std::to_string((long long)u->eng->option(o, -7));
+    po.for_each([&](const char*, int64_t v) { key += "_" + std::to_string((long long)v); });
     if (lane) key += "_lane" + std::to_string(lane);   // a second, independent activation set of the same shape (concurrent half-batches)
     auto it = u->plans.find(key);
     if (it != u->plans.end()) { it->second->last_use = ++u->use_clock; *out = it->second.get(); return TD_OK; }
@@ -796,9 +833,6 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
     pl.N = N; pl.H = H; pl.W = W;
     const size_t es = u->esize();
     const int chunk = u->chunk;
-    const bool use_splitk = u->eng->option("splitk", 1) != 0;
-    const int64_t splitk_target = u->eng->option("splitk_target_wgs", 512);
-    const int64_t bn128_min = u->eng->option("bn128_min_wgs", 128);
     int rc;
     size_t partial_bytes = 0;
 
@@ -813,7 +847,7 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         return TD_OK;
     };
 
-    // emits one fused conv op; decides tile shape / split-K; allocates its output (unless out_f32 target given)
+    // emits one fused conv op: wires its segments, lets conv_select choose kernel / tile / split-K, allocates its output (unless out_f32 target given)
     auto conv = [&](const std::string& label, std::vector<SegSpec> segs, int h, int w, int epi, int cvec_off, const Tensor* res, int res_resample,
                     bool res_norm, float clip, bool want_sumsq, bool out_f32, Tensor* outT) -> int {
         auto wit = u->convw.find(label);
@@ -843,211 +877,23 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         }
         p.wpack = cw.packed->p;
         p.N = N; p.H = h; p.W = w; p.Cout = cw.cout; p.CoutPad = cw.cout_pad; p.kgroups = kgroups;
-        op.narrow = w < 16;
-        // throughput flavour (bf16, conv_glds.hip).  Two tile variants: "big" = 8 waves on 256 pixels (16x16, or 8x8 x 4 images),
-        // one workgroup per CU; "small" = 4 waves on 128 pixels (8x16, or 8x8 x 2 images), two workgroups per CU.  Measured on
-        // MI355X (tools/conv_bench.hip sweeps): equal when the grid is >= 4 workgroups per CU, "small" wins below that (8x8 / 16x16
-        // levels of a 64-tile batch, everything at batch <= 8), and couts go in 128s unless that leaves < 2 workgroups per CU.
-        // Every variant accumulates a given output in the same K order with the same MFMA, so they are bit-identical to each other.
-        {
-            const int TW2 = op.narrow ? 8 : 16;
-            const bool c128 = cw.cout_pad % 128 == 0, c96 = cw.cout_pad % 96 == 0;
-            auto tiles = [&](int TH, int NIMG) { return (int64_t)((w + TW2 - 1) / TW2) * ((h + TH - 1) / TH) * ((N + NIMG - 1) / NIMG); };
-            // couts in 128s / 96s; 64s (cout_pad is always a multiple of 64) on 16-wide maps for the layers neither divides: the decoder's 64- and
-            // 320-channel levels and the few-channel output convs, which would otherwise run on the per-tap flavour (option "glds_bn64")
-            const bool c64 = !op.narrow && u->eng->option("glds_bn64", 1) != 0;
-            auto pick_bn = [&](int64_t mt) { return (c128 && (mt * (cw.cout_pad / 128) >= 512 || !c96)) ? 128 : (c96 ? 96 : (c64 ? 64 : 0)); };
-            const int64_t mt_big = tiles(op.narrow ? 8 : 16, op.narrow ? 4 : 1), mt_small = tiles(8, op.narrow ? 2 : 1);
-            int variant = 0, bn2 = pick_bn(mt_big);
-            if (bn2 && mt_big * (cw.cout_pad / bn2) < 1024) { variant = 1; bn2 = pick_bn(mt_small); }
-            // short K loops (<= "glds_small_max_groups" K-groups): prologue and epilogue dominate a workgroup's life, two independent small
-            // workgroups per CU overlap them (decoder 512x512 / 256x256 levels: 64- and 128-channel convs)
-            if (bn2 && !op.narrow && kgroups <= u->eng->option("glds_small_max_groups", 6)) { variant = 1; bn2 = pick_bn(mt_small); }
-            // test hooks: "glds_variant" = 0 (big) / 1 (small) and "glds_bn" = 96 / 128 force the tile shape wherever it is legal
-            // (tests assert that every legal shape gives bit-identical results: same K order, same MFMA)
-            const int64_t fv = u->eng->option("glds_variant", -1), fbn = u->eng->option("glds_bn", 0);
-            if (bn2 && (fv == 0 || fv == 1)) { variant = (int)fv; bn2 = pick_bn(variant ? mt_small : mt_big); }
-            if (bn2 && ((fbn == 128 && c128) || (fbn == 96 && c96) || (fbn == 64 && c64))) bn2 = (int)fbn;
-            const int64_t mt2 = variant ? mt_small : mt_big;
-            // "batch_invariant": kernel flavour and K order do not depend on the batch size (no split-K, LDS-DMA flavour whenever it
-            // applies), so a window's result is bit-identical whatever other windows share its batch / GPU.
-            const bool inv = u->eng->option("batch_invariant", 0) != 0;
-            // round quantisation: when both cout tilings are legal, 96s win if they turn a partial last round of the CU slots into full rounds
-            // (768-cout layers at 16x16, batch 64: 768 workgroups of 128 couts = 1.5 rounds of 512 slots, 1024 of 96 couts = 2.0 rounds of
-            // workgroups that are 3/4 as long); the tile shape never changes the bits
-            if (bn2 == 128 && c96 && fbn == 0 && u->eng->option("glds_round_aware", 1) != 0) {
-                const int64_t slots_ = variant ? 512 : 256, w128 = mt2 * (cw.cout_pad / 128), w96 = mt2 * (cw.cout_pad / 96);
-                const double t128 = (double)((w128 + slots_ - 1) / slots_) * 128.0, t96 = (double)((w96 + slots_ - 1) / slots_) * 96.0 * 1.03;
-                if (t96 < 0.9 * t128) bn2 = 96;
-            }
-            // (grids below "glds_min_wgs" used to fall to the per-tap flavour; with the small-batch flavour available they enter here and take it)
-            // The small-batch flavour's own conditions are evaluated HERE: a grid below "glds_min_wgs" may only enter the branch when that flavour
-            // will really take it -- otherwise it falls to the per-tap flavour as before (it used to stay on conv_glds with a tiny grid)
-            bool sb_avail = u->bf16 && !inv && u->eng->option("sb", 1) != 0 && cw.sb_n3 >= 0;
-            for (const SegSpec& sg : segs) if (sg.taps != 9 && sg.xform != 0) sb_avail = false;   // its 1x1 K-groups go straight from global memory to the MFMA
-            const bool sb_takes = sb_avail && bn2 && mt2 * (cw.cout_pad / bn2) * 2 <= (variant ? 512 : 256) && mt2 * (cw.cout_pad / bn2) <= u->eng->option("sb_max_glds_wgs", 1 << 30);
-            if (u->bf16 && bn2 && u->eng->option("glds", 1) && (inv || sb_takes || mt2 * (cw.cout_pad / bn2) >= u->eng->option("glds_min_wgs", 8))) {
-                op.flavor = 2; op.bn = bn2; op.glds_variant = variant;
-                int TH2 = variant ? 8 : (op.narrow ? 8 : 16);
-                const int NIMG2 = op.narrow ? (variant ? 2 : 4) : 1;
-                p.tiles_x = (w + TW2 - 1) / TW2; p.tiles_y = (h + TH2 - 1) / TH2; p.img_groups = (N + NIMG2 - 1) / NIMG2;
-                p.n_ntiles = cw.cout_pad / bn2; p.ksplit = 1;
-                // too few workgroups to give every SIMD two waves (8x8 level of a 64-tile batch, small batches): split K, the fp32
-                // partials are summed in fixed order by conv_splitk_reduce_kernel (not in batch_invariant mode: the K order changes)
-                const int64_t wgs = mt2 * p.n_ntiles, slots = variant ? 512 : 256;
-                const bool may_split = !inv && use_splitk && u->eng->option("glds_splitk", 1) && wgs * 2 <= slots;
-                if (may_split && kgroups >= u->eng->option("glds_splitk_from_groups", 2))
-                    p.ksplit = (int)std::min<int64_t>(std::min<int64_t>(u->eng->option("glds_splitk_max", 32), kgroups / std::max<int64_t>(1, u->eng->option("glds_splitk_min_groups", 1))), slots / wgs);
-                // Latency regime, 16-wide maps (round 3, option "glds_tiny"): in the split-K regime the fp32 partial slabs dominate the traffic -- at
-                // batch 1 a forward wrote 0.95 GB and read 1.7 GB against 0.5 GB of weights (profiles/r03_batch1_hbm_traffic.json).  A "tiny" tile
-                // (64 px x 64 couts, 4 waves) fills the chip with (pixel tile, cout tile) workgroups instead of K slices: K is split only as far as
-                // it takes to reach ~1.5 workgroups per CU (64x64 level of one tile: no split at all).  tools/b1_tiny.sh: 18 -> 12 us (192->192 at
-                // 64x64), 31 -> 21 us (384->384), 25 -> 19.5 us (768->384 at 32x32) incl. the reduce launch.  Same K order and MFMA per output as
-                // every other shape (bit-identical when neither splits K).
-                if (may_split && !op.narrow && variant == 1 && u->eng->option("glds_tiny", 0) != 0) {
-                    const int64_t wgs_tiny = tiles(4, 1) * (cw.cout_pad / 64);
-                    if (wgs_tiny <= 384) {
-                        op.glds_variant = 2; op.bn = 64; TH2 = 4;
-                        p.tiles_y = (h + TH2 - 1) / TH2; p.n_ntiles = cw.cout_pad / 64;
-                        p.ksplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kgroups, u->eng->option("glds_splitk_max", 32)), 384 / wgs_tiny));
-                    }
-                }
-                // Wide tile (conv_glds_wide.hip, round 6): 256 px x 96 / 64 couts on 4 waves, two workgroups per CU, 32-channel K-groups with a double-buffered
-                // patch -- half the weight bytes per MFMA through the CU's L2 -> LDS path, 0.6x the LDS fragment reads, half as many workgroup
-                // prologues / epilogue drains, no restage barrier.  Taken where its grid still gives every CU slot >= "glds_wide_min_wgs" / 512 workgroups
-                // (the 64x64, 32x32 and 16x16 levels of a 64-window batch -- 384 workgroups of 256 pixels there are one round on 3/4 of the slots where 768 of 128 pixels
-                // are one and a half rounds: +0.9 % on the bench line, tools/r06_exp3.sh --, the decoder's 512x512 / 256x256 levels) for launches it serves at full speed: 3x3
-                // K-segments, optionally followed by untransformed 1x1 segments (streamed by LDS-DMA), 16-bit output in 16-byte runs.  Another K order than the other tiles (channel half outside the
-                // taps): never in batch_invariant mode, where the choice must not depend on the batch.  Option "glds_wide": 0 never, 1 this rule, 2 wherever legal.
-                {
-                    const int64_t wmode = u->eng->option("glds_wide", 1);
-                    const int bnw = cw.cout_pad % 96 == 0 ? 96 : (cw.cout_pad % 64 == 0 ? 64 : 0);
-                    // A 1x1 tail (the decoder blocks' fused skip conv) is streamed by LDS-DMA on the wide tile as well, when its sources need no transform at staging.
-                    // Measured (tools/r06_exp7.sh): level with conv_glds's stream on the base model's 192 / 384-cout layers (360.7 vs 360.8, 320.1 vs 320.5, 267.8 vs
-                    // 266.9 us), a loss at the 16x16 level (134 -> 145 us) and -1.4 % on the bench line with two lanes; +10 % on the decoder model's 64-cout layers
-                    // (268 -> 242 us) and +1.7 % on the cascade.  Hence: tails on the wide tile for the 64-cout tile only.  "glds_wide_tail": 0 never, 1 this rule, 2 always.
-                    const int64_t tmode = u->eng->option("glds_wide_tail", 1);
-                    bool pure3 = true;
-                    for (const SegSpec& sg : segs) if (sg.taps != 9 && (sg.xform != 0 || tmode == 0 || (tmode == 1 && bnw != 64))) pure3 = false;
-                    const int64_t wgs_w = bnw ? tiles(16, 1) * (cw.cout_pad / bnw) : 0;
-                    if (wmode != 0 && !inv && fv < 0 && fbn == 0 && !op.narrow && p.ksplit == 1 && bnw && !out_f32 && (cw.cout & 7) == 0 && p.nseg <= 3 && (pure3 || wmode == 2) &&
-                        (wmode == 2 || wgs_w >= u->eng->option("glds_wide_min_wgs", 384))) {
-                        op.glds_variant = 3; op.bn = bnw;
-                        p.tiles_x = (w + 15) / 16; p.tiles_y = (h + 15) / 16; p.img_groups = N; p.n_ntiles = cw.cout_pad / bnw;
-                        // Persistent tile loop of the wide tile (option "glds_wide_persist", default 0): 2 x CUs workgroups walk the launch's tiles, the next tile's first
-                        // patch, modulation row and weight half tiles requested under the current tile's taps, staging split by wave (two waves stream weights, two stage
-                        // patches).  Exists for the 64-cout tile, pure 3x3 launches over whole 16 x 16 tiles.  Bit-identical to the one-tile-per-workgroup form and,
-                        // measured, not faster (profiles/r06_wide_tile_persistent_loop.txt) -- which is why it is off.
-                        bool tail3 = false;
-                        for (const SegSpec& sg : segs) if (sg.taps != 9) tail3 = true;
-                        if (u->eng->option("glds_wide_persist", 0) != 0 && bnw == 64 && !tail3 && (h & 15) == 0 && (w & 15) == 0 && cw.cout == cw.cout_pad)
-                            p.persist = conv_wide_persist_grid((long long)p.tiles_x * p.tiles_y * N * p.n_ntiles, 2 * std::max(1, u->eng->n_cus));
-                        // The 96-cout, pure-3x3, one-tile-per-workgroup launches -- two thirds of a grid forward's conv time -- exist a second time on the
-                        // 16x16x32 MFMA shape (conv_glds_wide16.hip: same tile and pipeline, one 32-deep step per half K-step; another fp32 summation order).
-                        // Option "glds_wide_mfma16": 0 the 32x32x16 kernel everywhere, 1 the 16x16x32 kernel for these launches (profiles/wide_mfma16_ab.txt).
-                        op.wide16 = u->eng->option("glds_wide_mfma16", 1) != 0 && bnw == 96 && !tail3 && p.persist == 0;
-                    }
-                }
-                // Small-batch flavour (conv_sb.hip, round 4) wherever the throughput tiles do not fill the chip (workgroups x 2 <= CU slots: the
-                // launches that used to split K over WORKGROUPS).  K is split over the four waves of a workgroup and reduced through LDS: no fp32
-                // partial planes in HBM, no reduce launch (BASELINE configs[1]: one tile x 20 steps; the 1-16-window batches of the cascade's latent
-                // stage).  Tile: 64 px x 64 couts when that gives "sb_target_wgs" workgroups, else 64 x 32, else 32 x 32.  The weight-streaming-bound
-                // deep levels (one tile: 8x8 and 16x16 maps, 6 - 21 MB of weights per conv against 24 - 144 workgroups that each ingest <= ~85 GB/s)
-                // additionally split K over workgroups, 64 x 32 tiles, ~224 workgroups in all: the partial planes there are small (64 - 256 pixels)
-                // and the reduce launch costs less than the weight stream gains (tools/sb_splitk.sh: 8x8 1536->768 39 -> 17 us cold).
-                // Not in batch_invariant mode (conv_glds stays pinned): the K order differs, so the choice must not depend on the batch.
-                if (op.flavor == 2 && sb_takes && op.glds_variant != 3) {
-                    {
-                        const int TWs = op.narrow ? 8 : 16;
-                        auto th_of = [&](int mt) { return op.narrow ? (mt == 2 ? 8 : 4) : (mt == 4 ? 8 : mt == 2 ? 4 : 2); };
-                        auto sb_wgs = [&](int mt, int nt) { return (int64_t)((w + TWs - 1) / TWs) * ((h + th_of(mt) - 1) / th_of(mt)) * N * (cw.cout_pad / (32 * nt)); };
-                        const int64_t target = u->eng->option("sb_target_wgs", 160);
-                        int mt = 1, nt = 1, ks = 1;
-                        // round 5: a 128 px x 32 cout tile exists for the launches where 64 x 64 would be chosen and it gives as many workgroups (31 % fewer
-                        // ingested bytes per workgroup and K-group).  OFF by default (option sb_m4 = 1 takes it): measured level -- -0.3 % / -1 % of a forward at
-                        // batch 1 / 2, +2.5 % at batch 8, +1 % at 16, -1 % at 32 (profiles/r05_conv_sb_128px_tile.txt)
-                        if (!op.narrow && u->eng->option("sb_m4", 0) != 0 && sb_wgs(2, 2) >= target && sb_wgs(4, 1) >= target) { mt = 4; nt = 1; }
-                        else if (sb_wgs(2, 2) >= target) { mt = 2; nt = 2; } else if (sb_wgs(2, 1) >= target) { mt = 2; nt = 1; }
-                        else if (use_splitk && u->eng->option("sb_splitk", 1) != 0 && sb_wgs(2, 1) * 2 <= u->eng->option("sb_splitk_wgs", 224)) {
-                            mt = 2; nt = 1;
-                            ks = (int)std::min<int64_t>(std::min<int64_t>(kgroups, u->eng->option("sb_splitk_max", 16)), (u->eng->option("sb_splitk_wgs", 224) + sb_wgs(2, 1) / 2) / sb_wgs(2, 1));
-                        }
-                        const int64_t fmt = u->eng->option("sb_mt", 0), fnt = u->eng->option("sb_nt", 0);   // test hooks
-                        if (fmt == 1 || fmt == 2 || (fmt == 4 && !op.narrow)) { mt = (int)fmt; ks = 1; }
-                        if (fnt == 1 || fnt == 2) { nt = (int)fnt; ks = 1; if (mt == 4 && fnt == 2 && fmt != 4) mt = 2; }
-                        if (mt == 4) nt = 1;   // (the 128-pixel tile exists with 32 couts only)
-                        // Round 5: the launches that would split K over workgroups on top (the weight-streaming-bound 8x8 / 16x16 levels of one or
-                        // two tiles) take the deep-level latency flavour instead (conv_s16.hip: 64 px x 16 couts, twice the workgroups per weight
-                        // byte, no partial planes, no reduce launch).  Option "s16": 1 = there (default), 0 = never, 2 = wherever conv_sb applies (test hook).
-                        const int64_t s16_mode = u->eng->option("s16", 1);
-                        // Measured (profiles/r05_conv_s16_deep_levels.txt): it wins where its own grid reaches about half the chip (16x16 level of one tile:
-                        // 144 workgroups, 8.9 against 10.1 us for 576 -> 576) and loses where it does not (8x8 level: 48 workgroups each streaming
-                        // 16 x K weights with 36 KB in flight per CU: 12.1 against 9.0 us) -- there split-K over workgroups stays.
-                        const int64_t wgs16 = sb_wgs(2, 1) * 2;
-                        const bool s16 = s16_mode == 2 || (s16_mode == 1 && fmt == 0 && fnt == 0 && sb_wgs(2, 2) < target && sb_wgs(2, 1) < target &&
-                                                           wgs16 <= u->eng->option("sb_splitk_wgs", 224) && wgs16 >= u->eng->option("s16_min_wgs", 128));
-                        if (s16) {
-                            if ((rc = ensure_packed_s16(u, cw))) return rc;
-                            op.flavor = 5; op.sb_mt = 2; op.sb_nt = 0; p.ksplit = 1;
-                            p.tiles_x = (w + TWs - 1) / TWs; p.tiles_y = (h + th_of(2) - 1) / th_of(2); p.img_groups = N; p.n_ntiles = cw.cout_pad / 16;
-                            p.wpack_sb = cw.packed_s16->p; p.sb_n3 = cw.sb_n3;
-                        } else {
-                        if ((rc = ensure_packed_sb(u, cw))) return rc;
-                        op.flavor = 4; op.sb_mt = mt; op.sb_nt = nt; p.ksplit = ks < 1 ? 1 : ks;
-                        p.tiles_x = (w + TWs - 1) / TWs; p.tiles_y = (h + th_of(mt) - 1) / th_of(mt); p.img_groups = N; p.n_ntiles = cw.cout_pad / (32 * nt);
-                        p.wpack_sb = cw.packed_sb->p; p.sb_n3 = cw.sb_n3;
-                        }
-                        // workgroup order (speed only): the operand that is larger decides which siblings share an XCD's L2.  Weights (every layer
-                        // of a single tile: 0.2 - 21 MB against <= 4.7 MB of activations): the pixel tiles of a cout tile are adjacent, so an XCD
-                        // fetches few cout tiles' weights instead of all of them (batch 1: 1636 -> 1121 MB fetched per forward, tools/r04_order.sh);
-                        // activations (larger batches): the cout tiles of a pixel tile are adjacent and share the halo patch.  Option sb_order forces.
-                        {
-                            double wbytes = 0.0, abytes = 0.0;
-                            for (int i = 0; i < p.nseg; ++i) {
-                                wbytes += (double)(p.seg[i].C / chunk) * p.seg[i].taps * cw.cout_pad * 128.0;
-                                abytes += (double)N * p.seg[i].Hs * p.seg[i].Ws * p.seg[i].C * 2.0;
-                            }
-                            const int64_t fo = u->eng->option("sb_order", -1);
-                            p.sb_order = fo == 0 || fo == 1 ? (int)fo : (wbytes >= abytes ? 1 : 0);
-                        }
-                    }
-                }
-            }
-        }
-        if (op.flavor == 0) {
-            const int TH = 8, TW = op.narrow ? 8 : 16, NIMG = op.narrow ? 2 : 1;
-            p.tiles_x = (w + TW - 1) / TW; p.tiles_y = (h + TH - 1) / TH; p.img_groups = (N + NIMG - 1) / NIMG;
-            const int64_t mt = (int64_t)p.tiles_x * p.tiles_y * p.img_groups;
-            op.bn = 64;
-            const bool inv0 = u->eng->option("batch_invariant", 0) != 0;
-            // batch_invariant: the cout tile must not depend on the batch size either -- this flavour keeps its pixel-norm partials per
-            // (cout tile, wave column), so a different bn would change the order in which the consumer adds the sums of squares
-            if (cw.cout_pad % 128 == 0 && (inv0 || mt * (cw.cout_pad / 128) >= bn128_min)) op.bn = 128;
-            else if (cw.cout_pad % 96 == 0 && (inv0 || mt * (cw.cout_pad / 96) >= bn128_min)) op.bn = 96;
-            p.n_ntiles = cw.cout_pad / op.bn;
-            const int64_t base = mt * p.n_ntiles;
-            p.ksplit = 1;
-            if (use_splitk && !u->eng->option("batch_invariant", 0) && base < splitk_target / 2 && kgroups > 1) p.ksplit = (int)std::min<int64_t>(kgroups, (splitk_target + base - 1) / base);
-        }
-        // Few-cout flavour (conv_fewcout.hip, round 6): an fp32-output 3x3 conv with <= 4 real couts (the decoder model's 64 -> 1 output conv) does its
-        // multiply-adds on the VALU, one pixel per thread, instead of a 64-cout MFMA tile for one cout.  Maps of >= 128 x 128 pixels (a rule of the shape
-        // only: also legal in batch_invariant mode); option "fewcout" = 0 keeps the MFMA tile.  If the sampler later fuses its solver step into this conv
-        // (EPI_DPM_STEP), the same kernel runs the step in its epilogue: fused and unfused runs of the decoder model have the same bits.
-        if (u->eng->option("fewcout", 1) != 0 && (u->dt == 1 || u->dt == 2) && out_f32 && epi == EPI_PLAIN && cw.cout <= 4 && segs.size() == 1 && segs[0].taps == 9 &&
-            segs[0].xform == 0 && p.seg[0].resample == 0 && p.seg[0].Hs == h && p.seg[0].Ws == w && !res && clip <= 0.f && (int64_t)h * w >= 128 * 128 && w >= 16) {
-            op.flavor = 6; op.bn = 64; op.glds_variant = 0; op.narrow = false;
-            p.tiles_x = (w + 15) / 16; p.tiles_y = (h + 15) / 16; p.img_groups = N; p.n_ntiles = 1; p.ksplit = 1; p.persist = 0;
-        }
-        if (p.ksplit > 64) p.ksplit = 64;
-        if (!conv_set_kbounds(p, u->eng->option("splitk_weighted", 1) != 0, chunk)) return fail(TD_ERR_UNSUPPORTED, "split-K bounds: " + label);
+        // kernel, tile and split: conv_select.h decides from the shape, the weights' geometry and the plan options
+        ConvSelIn in;
+        in.N = N; in.h = h; in.w = w; in.cout = cw.cout; in.cout_pad = cw.cout_pad; in.kgroups = kgroups; in.nseg = p.nseg;
+        for (int i = 0; i < p.nseg; ++i) in.seg[i] = {p.seg[i].C, p.seg[i].taps, p.seg[i].xform, p.seg[i].resample, p.seg[i].Hs, p.seg[i].Ws};
+        in.chunk = chunk; in.dt = u->dt; in.bf16 = u->bf16; in.sb_n3 = cw.sb_n3; in.out_f32 = out_f32; in.epi = epi; in.has_res = res != nullptr; in.clip_pos = clip > 0.f;
+        in.n_cus = u->eng->n_cus; in.op_index = (int)pl.ops.size();
+        const ConvSel& sel = op.sel = conv_select(in, po);
+        p.tiles_x = sel.tiles_x; p.tiles_y = sel.tiles_y; p.img_groups = sel.img_groups; p.n_ntiles = sel.n_ntiles; p.ksplit = sel.ksplit;
+        p.persist = sel.persist; p.sb_order = sel.sb_order; p.reverse = sel.reverse; p.dma1x1 = sel.dma1x1;
+        if (sel.wcopy == ConvWeightCopy::Sb) { if ((rc = ensure_packed_sb(u, cw))) return rc; p.wpack_sb = cw.packed_sb->p; p.sb_n3 = cw.sb_n3; }
+        if (sel.wcopy == ConvWeightCopy::S16) { if ((rc = ensure_packed_s16(u, cw))) return rc; p.wpack_sb = cw.packed_s16->p; p.sb_n3 = cw.sb_n3; }
+        if (!conv_set_kbounds(p, po.splitk_weighted != 0, chunk)) return fail(TD_ERR_UNSUPPORTED, "split-K bounds: " + label);
         p.epi = epi; p.out_f32 = out_f32 ? 1 : 0; p.clip = clip; p.zeros = u->eng->zeros;
-        // pixel-norm partials of the output: the LDS-DMA and small-batch flavours write one per 32-cout MFMA block, the 64 x 16 flavour one per 16 couts (independent of the tile shape),
-        // the per-tap flavour one per (cout tile, wave column), the split-K reduce kernel one per 256 couts
-        const int out_parts = p.ksplit > 1 ? (cw.cout_pad + 255) / 256 : op.flavor == 5 ? cw.cout_pad / 16 : (op.flavor >= 2 ? cw.cout_pad / 32 : p.n_ntiles * 2);
         if (out_f32) {
             outT->C = cw.cout; outT->cstride = 8; outT->H = h; outT->W = w; outT->sumsq = nullptr;
             if ((rc = new_buf(pl, (size_t)N * h * w * 8 * 4, &outT->ptr))) return rc;
-        } else if ((rc = new_tensor(cw.cout, h, w, want_sumsq, out_parts, outT))) return rc;
+        } else if ((rc = new_tensor(cw.cout, h, w, want_sumsq, sel.out_parts, outT))) return rc;
         p.out = outT->ptr; p.out_cstride = outT->cstride; p.out_sumsq = outT->sumsq;
         if ((size_t)N * h * w * (size_t)std::max(outT->cstride, cw.cout_pad) >= ((size_t)1 << 31))
             return fail(TD_ERR_ARG, "batch too large for 32-bit activation addressing (output of " + label + "): split the batch");
@@ -1062,19 +908,13 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         }
         if (p.ksplit > 1) partial_bytes = std::max(partial_bytes, (size_t)p.ksplit * N * h * w * cw.cout_pad * 4);
         op.out_C = cw.cout; op.out_H = h; op.out_W = w;
-        // alternate the walk order of the workgroup grid from conv to conv (option "walk_alternate", speed only): a layer then starts with the
-        // rows its producer wrote last, which are still in the 256 MB Infinity Cache (profiles/r03_conv_walk_order_and_stagger.txt)
-        if (op.flavor == 2 && u->eng->option("walk_alternate", 1) != 0) p.reverse = (int)(pl.ops.size() & 1);
-        // 1x1 segments by LDS-DMA where the launch qualifies (launch_glds_cfg).  Split-K slices of one or two K-groups (batch 1) do not amortise the
-        // stream's start-up (a barrier and one exposed round trip): measured -0.5 % there, -19 % with 18 groups per slice (8x8 level at batch 64)
-        if (op.flavor == 2) p.dma1x1 = (u->eng->option("glds_dma1x1", 1) != 0 && (p.ksplit == 1 || p.kgroups >= 4 * p.ksplit)) ? 1 : 0;
         pl.ops.push_back(op);
         return TD_OK;
     };
 
     // bf16 mode: attention blocks run on the MFMA kernel (attn_mfma.hip); its packed operands live in a per-op workspace.  Everything else -- fp16, fp32, and bf16
     // with option attn_mfma = 0 -- runs the scalar attn_kernel (small_kernels.hip), whose LDS tiles hold 64 tokens: more is refused here, before anything is launched
-    const bool attn_on_mfma = u->dt == TD_DTYPE_BF16 && u->eng->option("attn_mfma", 1) != 0;
+    const bool attn_on_mfma = u->dt == TD_DTYPE_BF16 && po.attn_mfma != 0;
     auto attn_fits = [&](int tokens, const std::string& name) -> int {
         // (the autoencoder graphs run such a block on the one-wave-per-query kernel of ae_kernels.hip instead: run_unet)
         if (tokens > 65535) return fail(TD_ERR_UNSUPPORTED, "attention over more than 65535 tokens: " + name);
@@ -1181,7 +1021,7 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
     // and the skip tensor of the concatenation) reads a second copy that the PRODUCER's epilogue writes already activated, instead of
     // applying exp/rcp to every 16-byte piece of every halo patch in every cout-tile workgroup of the consumer.  One copy per
     // producer (the first such consumer's scale); computed from the rounded output, so results are bit-identical to the in-kernel form.
-    if (u->eng->option("producer_act", 1)) {
+    if (po.producer_act) {
         std::unordered_map<const void*, size_t> producer;
         for (size_t k = 0; k < pl.ops.size(); ++k)
             if (pl.ops[k].kind == Op::CONV && !pl.ops[k].p.out_f32) producer[pl.ops[k].p.out] = k;
@@ -1267,6 +1107,19 @@ static int compute_cvecs(td_unet* u, Plan& pl, const std::vector<float>& t_steps
     return TD_OK;
 }
 
+static hipError_t launch_selected(const ConvParams& p, const ConvSel& s, int dt, hipStream_t st) {
+    switch (s.kernel) {
+        case ConvKernel::PerTap: return launch_conv(p, dt, s.narrow, s.bn, 0, st);
+        case ConvKernel::Glds: return launch_conv_glds(p, dt, s.narrow, s.bn, s.glds_variant, st);
+        case ConvKernel::GldsWide: return launch_conv_glds_wide(p, dt, s.bn, st);
+        case ConvKernel::GldsWide16: return launch_conv_glds_wide16(p, dt, st);
+        case ConvKernel::Sb: return launch_conv_sb(p, dt, s.narrow, s.sb_mt, s.sb_nt, st);
+        case ConvKernel::S16: return launch_conv_s16(p, dt, s.narrow, st);
+        case ConvKernel::FewCout: return launch_conv_fewcout(p, dt, st);   // with the solver step fused too: the same sums as the plain launch, then epilogue4's step
+    }
+    return hipErrorInvalidValue;
+}
+
 // runs the conv stack: xin -> F, using modulation vectors of `step`
 // `fuse` (EDM sampler): the output conv runs the DPM-Solver++ update of this step in its epilogue (EPI_DPM_STEP) instead of writing F
 static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = nullptr) {
@@ -1320,12 +1173,8 @@ static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = null
             p.epi = EPI_DPM_STEP; p.dpm_x = (float*)pl.x->p; p.dpm_m1 = (float*)pl.m1->p; p.dpm_m2 = u->eng->option("solver_order", 2) == 3 ? (float*)pl.m2->p : nullptr; p.dpm_xin = pl.xin; p.dpm_xin_cstride = u->chunk; p.dpm_k = *fuse;
         }
         mark();
-        hipError_t e = op.flavor == 6 ? launch_conv_fewcout(p, u->dt, st)   // with the solver step fused too: the same sums as the plain launch, then epilogue4's step
-                       : op.flavor == 5 ? launch_conv_s16(p, u->dt, op.narrow, st)
-                       : op.flavor == 4 ? launch_conv_sb(p, u->dt, op.narrow, op.sb_mt, op.sb_nt, st)
-                       : op.flavor == 2 ? (op.glds_variant == 3 ? (op.wide16 ? launch_conv_glds_wide16(p, u->dt, st) : launch_conv_glds_wide(p, u->dt, op.bn, st)) : launch_conv_glds(p, u->dt, op.narrow, op.bn, op.glds_variant, st))
-                       : launch_conv(p, u->dt, op.narrow, op.bn, 0, st);
-        mark(); if (prof) { ev_kind.push_back(0); char tag[160]; double gf_ = op.k_alg * 2.0 * p.N * p.H * p.W * p.Cout * 1e-9;  /* algorithmic GFLOP of this launch: REAL input channels (the 6-channel input conv is 5.4 GFLOP at batch 64, not the 58 its K padding to 64 would give) */
+        hipError_t e = launch_selected(p, op.sel, u->dt, st);
+        mark(); if (prof) { ev_kind.push_back(0); char head[48], nums[112]; double gf_ = op.k_alg * 2.0 * p.N * p.H * p.W * p.Cout * 1e-9;  /* algorithmic GFLOP of this launch: REAL input channels (the 6-channel input conv is 5.4 GFLOP at batch 64, not the 58 its K padding to 64 would give) */
             /* algorithmic HBM megabytes of this launch: every source tensor once (at ITS resolution), the residual once, the outputs once, the weights once */
             double mb_ = 0.0; const double es_ = (double)u->esize();
             for (int si_ = 0; si_ < p.nseg; ++si_) mb_ += (double)p.N * p.seg[si_].Hs * p.seg[si_].Ws * p.seg[si_].C * es_ + (double)p.seg[si_].C / 64.0 * p.seg[si_].taps * p.CoutPad * 128.0 * (es_ / 2.0);
@@ -1334,8 +1183,10 @@ static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = null
             const double mbs_ = (mb_ + o1_) * 1e-6;   /* strict: without the optional pre-activated second output (an optimisation, not part of the layer's definition) */
             mb_ += o1_ * (p.out2 ? 2.0 : 1.0);
             mb_ *= 1e-6;
-            snprintf(tag, sizeof tag, " [%dx%d k%d f%d%s bn%d wg%d ks%d gf%.2f mb%.2f mbs%.2f%s]", p.H, p.W, p.kgroups, op.flavor, op.flavor == 5 ? "c16" : op.flavor == 4 ? (op.sb_mt == 4 ? "m4n1" : op.sb_mt == 2 ? (op.sb_nt == 2 ? "m2n2" : "m2n1") : (op.sb_nt == 2 ? "m1n2" : "m1n1")) : op.flavor == 2 ? (op.glds_variant == 3 ? (p.persist > 0 ? "wp" : "w") : op.glds_variant == 2 ? "t" : op.glds_variant ? "s" : "b") : "", op.bn, p.n_ntiles * p.tiles_x * p.tiles_y * p.img_groups, p.ksplit, gf_, mb_, mbs_, (op.flavor == 2 && op.glds_variant == 3 && op.wide16) ? " x16" : ""); ev_label.push_back(op.label + tag);   /* x16: conv_glds_wide16.hip; the flavour tag stays f2w */
-            ev_flop.push_back(op.flavor == 2 ? 2.0 * p.N * p.H * p.W * (double)p.Cout * op.k_alg : 0.0); }   // the LDS-DMA family alone (bench.py's roofline kernel); small-batch launches are told apart by their f4 label
+            snprintf(head, sizeof head, " [%dx%d k%d ", p.H, p.W, p.kgroups);
+            snprintf(nums, sizeof nums, " wg%d ks%d gf%.2f mb%.2f mbs%.2f", p.n_ntiles * p.tiles_x * p.tiles_y * p.img_groups, p.ksplit, gf_, mb_, mbs_);
+            ev_label.push_back(op.label + head + conv_sel_tag(op.sel, nums) + "]");   /* x16: conv_glds_wide16.hip; the flavour tag stays f2w */
+            ev_flop.push_back(op.sel.glds_family() ? 2.0 * p.N * p.H * p.W * (double)p.Cout * op.k_alg : 0.0); }   // the LDS-DMA family alone (bench.py's roofline kernel); small-batch launches are told apart by their f4 label
         if (e != hipSuccess) return fail(TD_ERR_HIP, "conv launch " + op.label + ": " + hipGetErrorString(e));
     }
     return TD_OK;
@@ -1592,7 +1443,8 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
     if (!strncmp(label, "sumsq:", 6)) {
         for (auto& op : pl->ops) {
             if (op.kind != Op::CONV || op.label != label + 6 || !op.p.out_sumsq) continue;
-            const int parts = op.p.ksplit > 1 ? (op.p.CoutPad + 255) / 256 : (op.flavor >= 2 ? op.p.CoutPad / 32 : op.p.n_ntiles * 2);
+            // (an S16 op keeps sel.out_parts = CoutPad / 16 planes; this read-back has always returned the first CoutPad / 32 of them, which is what its callers expect)
+            const int parts = op.sel.kernel == ConvKernel::S16 ? op.p.CoutPad / 32 : op.sel.out_parts;
             const size_t M = (size_t)n * op.out_H * op.out_W;
             dims[0] = parts; dims[1] = n; dims[2] = op.out_H; dims[3] = op.out_W;
             if ((int64_t)(parts * M) > capacity) return fail(TD_ERR_ARG, "capacity");
