@@ -25,3 +25,5 @@ from .explorer import (coarse_channels, colorize, relief_rgba8, raw_tile, land_t
 from .rivers import relief_overlay_map, smooth_bumps, river_relief_map, smooth_river_bumps  # noqa: F401  (get_relief_map stays relief.py's)
 from .custom_world import (rasterize_cells, fill_nearest, elevation_int16, h_to_meters, fill_nodata, rasterize_layer, azgaar_layers,  # noqa: F401
                            load_and_pad, import_conditioning, export_elevation)
+from .dataset import (fill_voids, block_median, laplacian_encode, land_share, moments, mask_voids, prepare_chunks, prepare_and_encode,  # noqa: F401
+                      RunningStats, calculate_stats_welford)
