@@ -27,3 +27,5 @@ from .custom_world import (rasterize_cells, fill_nearest, elevation_int16, h_to_
                            load_and_pad, import_conditioning, export_elevation)
 from .dataset import (fill_voids, block_median, laplacian_encode, land_share, moments, mask_voids, prepare_chunks, prepare_and_encode,  # noqa: F401
                       RunningStats, calculate_stats_welford)
+from .coarse_dataset import (area_resize_width, tile_stats, crop_scores, fill_oceans_device, fill_oceans, latitude_bands,  # noqa: F401
+                             build_coarse_bands)
