@@ -10,6 +10,8 @@
 
 namespace td {
 
+enum { EPI_PLAIN = 0, EPI_EMB_SILU = 1, EPI_RESIDUAL = 2, EPI_DPM_STEP = 3 };   // ConvParams::epi (td_device.h), ConvSelIn::epi, GraphOp::epi (model_graph.h)
+
 // Every engine option the plan builder reads, in the order of the harness's columns.  engine.hip's read_plan_options() reads each once (there the
 // shipped defaults live) and build_plan() puts every member into the plan-cache key: an option the builder reads is in the key by construction.
 #define TD_PLAN_OPTIONS(X)                                                                                                                          \

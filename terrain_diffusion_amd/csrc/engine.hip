@@ -14,6 +14,7 @@
 #include "../../include/td_engine.h"
 #include "td_device.h"
 #include "conv_select.h"
+#include "model_graph.h"
 
 // single translation unit: kernels are compiled together with the host runtime
 #include "conv_igemm.hip"
@@ -244,32 +245,15 @@ static int end_call(td_engine* e, std::vector<Buf>& hold, bool all_device) {
 }
 
 // ------------------------------------------------------------------------------------------------ model description
-struct Block {
-    std::string name;
-    bool is_conv = false;      // the plain first conv
-    bool enc = true;
-    int cin = 0, cout = 0;
-    int resample = 0;          // 0 keep 1 down 2 up
-    bool attn = false;
-    bool concat = false;
-    int skip_c = 0;
-    int cvec_off = 0;          // offset into the concatenated per-block c vectors
-};
-
-struct Param {
-    std::string name;
-    int ndim = 0;
-    int64_t shape[4] = {0, 0, 0, 0};
+struct Param : GraphParam {
     std::vector<float> data;
     bool set = false;
     int64_t numel() const { int64_t n = 1; for (int i = 0; i < ndim; ++i) n *= shape[i]; return n; }
 };
 
-// weights of one fused conv op: up to 3 K-segments, each a slice of a (folded) reference weight tensor
-struct WSeg {
+// weights of one fused conv op: its K-segments' weight side with the folded tensor each slices (valid during finalize)
+struct WSeg : GraphSeg {
     const std::vector<float>* w = nullptr;  // folded [cout][cin_tot][k][k]
-    int cin_tot = 0, cin_off = 0, c_real = 0, c_pad = 0, taps = 9;
-    float mul = 1.f;
 };
 struct ConvWeights {
     std::vector<WSeg> segs;
@@ -340,19 +324,15 @@ struct td_unet {
     // (emb_channels = 0: a block's epilogue is mp_silu(y), unet_block.py:133-134 -- run as EPI_EMB_SILU on a modulation row of 1.0f, which is exact):
     // 1: encoder only, out_conv on the bottleneck (edm_unet.py:107-139 with encode_only); 2: skip-less decoder behind a 1x1 decoder_conv (edm_autoencoder.py:86-103)
     int kind = 0;
-    int lpb_dec[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // kind 2: layers_per_block_decoder
-    std::string out_label = "out_conv", out_gain_name = "out_gain";   // kind 1: "encoder.out_conv" / "encoder.out_gain"
+    ModelGraph g;              // blocks, parameters and fused ops (model_graph.h): finalize packs its weight side, build_plan wires its activation side
     Buf d_ones;                // kinds 1 and 2: the all-ones modulation row every block reads (cvec stride 0)
     bool bf16 = false;         // 16-bit storage (bf16 OR fp16): 64-channel K chunks, LDS-DMA / small-batch conv flavours available
     int dt = TD_DTYPE_F32;     // TD_DTYPE_*
     int chunk = 32;            // channels per 128-byte K chunk
-    int emb_ch = 0, noise_dims = 0, c_total = 0;
-    std::vector<Block> enc, dec;
-    int final_c = 0;
     std::vector<Param> params;
     std::map<std::string, int> pindex;
     std::map<std::string, std::vector<float>> folded;
-    std::map<std::string, ConvWeights> convw;  // by op label
+    std::vector<ConvWeights> convw;   // by index into g.ops (attention ops own none)
     bool finalized = false;
     bool prefolded = false;    // parameters already carry the MP normalisation and gains (host folded them)
     // embedding weights on device (fp32)
@@ -365,160 +345,16 @@ struct td_unet {
     size_t esize() const { return bf16 ? 2 : 4; }
 };
 
-static void add_param(td_unet* u, const std::string& name, std::initializer_list<int64_t> shape) {
-    Param p;
-    p.name = name;
-    p.ndim = (int)shape.size();
-    int i = 0;
-    for (auto s : shape) p.shape[i++] = s;
-    u->pindex[name] = (int)u->params.size();
-    u->params.push_back(std::move(p));
-}
-
-// mirrors edm_unet.py:105-139 (block names are the reference's state-dict prefixes)
-static int build_blocks(td_unet* u) {
-    const td_unet_config& c = u->cfg;
-    if (c.n_levels < 1 || c.n_levels > 8) return fail(TD_ERR_ARG, "n_levels out of range");
-    int maxm = 0;
-    for (int l = 0; l < c.n_levels; ++l) maxm = std::max(maxm, c.channel_mults[l]);
-    u->emb_ch = c.emb_channels ? c.emb_channels : c.model_channels * maxm;
-    u->noise_dims = c.noise_emb_dims ? c.noise_emb_dims : c.model_channels;
-    auto has_attn = [&](int res) { for (int i = 0; i < c.n_attn_resolutions; ++i) if (c.attn_resolutions[i] == res) return true; return false; };
-    int cout = c.in_channels + 1;
-    for (int l = 0; l < c.n_levels; ++l) {
-        int ch = c.model_channels * c.channel_mults[l], res = c.image_size >> l;
-        std::string r = std::to_string(res) + "x" + std::to_string(res);
-        Block b;
-        if (l == 0) { b.name = "enc." + r + "_conv"; b.is_conv = true; b.cin = cout; b.cout = ch; cout = ch; }
-        else { b.name = "enc." + r + "_down"; b.cin = cout; b.cout = cout; b.resample = 1; }
-        u->enc.push_back(b);
-        for (int i = 0; i < c.layers_per_block[l]; ++i) {
-            Block k;
-            k.name = "enc." + r + "_block" + std::to_string(i);
-            k.cin = cout; k.cout = ch; k.attn = has_attn(res); cout = ch;
-            u->enc.push_back(k);
-        }
+// the model's graph (model_graph.h) and a slot for every parameter it names
+static int init_graph(td_unet* u, const int32_t* lpb_dec) {
+    int rc = build_model_graph(u->cfg, u->kind, lpb_dec, u->chunk, u->g);
+    if (rc) return fail(rc, u->g.err);
+    for (const GraphParam& gp : u->g.params) {
+        Param p;
+        static_cast<GraphParam&>(p) = gp;
+        u->pindex[p.name] = (int)u->params.size();
+        u->params.push_back(std::move(p));
     }
-    std::vector<int> skips;
-    for (auto& b : u->enc) skips.push_back(b.cout);
-    for (int l = c.n_levels - 1; l >= 0; --l) {
-        int ch = c.model_channels * c.channel_mults[l], res = c.image_size >> l;
-        std::string r = std::to_string(res) + "x" + std::to_string(res);
-        if (l == c.n_levels - 1) {
-            Block a; a.name = "dec." + r + "_in0"; a.enc = false; a.cin = a.cout = cout; a.attn = c.midblock_attention != 0; u->dec.push_back(a);
-            Block b; b.name = "dec." + r + "_in1"; b.enc = false; b.cin = b.cout = cout; u->dec.push_back(b);
-        } else {
-            Block a; a.name = "dec." + r + "_up"; a.enc = false; a.cin = a.cout = cout; a.resample = 2; u->dec.push_back(a);
-        }
-        for (int i = 0; i < c.layers_per_block[l] + 1; ++i) {
-            Block k;
-            k.name = "dec." + r + "_block" + std::to_string(i);
-            k.enc = false; k.concat = true; k.skip_c = skips.back(); skips.pop_back();
-            k.cin = cout + k.skip_c; k.cout = ch; k.attn = has_attn(res); cout = ch;
-            u->dec.push_back(k);
-        }
-    }
-    u->final_c = cout;
-    // expected parameters
-    add_param(u, "out_gain", {});
-    add_param(u, "noise_fourier.freqs", {u->noise_dims / 2});
-    add_param(u, "noise_linear.weight", {u->emb_ch, u->noise_dims});
-    if (c.n_cond < 0 || c.n_cond > 8) return fail(TD_ERR_ARG, "n_cond out of range");
-    for (int i = 0; i < c.n_cond; ++i) {
-        const std::string pre = "conditional_layers." + std::to_string(i);
-        if (c.cond_type[i] == 0) add_param(u, pre + ".weight", {u->emb_ch, c.cond_dims[i]});
-        else if (c.cond_type[i] == 1) {
-            add_param(u, pre + ".0.freqs", {c.cond_dims[i]});
-            add_param(u, pre + ".0.phases", {c.cond_dims[i]});
-            add_param(u, pre + ".1.weight", {u->emb_ch, c.cond_dims[i]});
-        } else return fail(TD_ERR_UNSUPPORTED, "conditional input type (embedding tables are not on the accelerated path)");
-    }
-    int coff = 0;
-    auto add_block = [&](Block& b) {
-        if (b.is_conv) { add_param(u, b.name + ".weight", {b.cout, b.cin, 3, 3}); return; }
-        b.cvec_off = coff; coff += b.cout;
-        add_param(u, b.name + ".emb_gain", {});
-        add_param(u, b.name + ".conv_res0.weight", {b.cout, b.enc ? b.cout : b.cin, 3, 3});
-        add_param(u, b.name + ".emb_linear.weight", {b.cout, u->emb_ch});
-        add_param(u, b.name + ".conv_res1.weight", {b.cout, b.cout, 3, 3});
-        if (b.cin != b.cout) add_param(u, b.name + ".conv_skip.weight", {b.cout, b.cin, 1, 1});
-        if (b.attn) {
-            add_param(u, b.name + ".attn_qkv.weight", {3 * b.cout, b.cout, 1, 1});
-            add_param(u, b.name + ".attn_proj.weight", {b.cout, b.cout, 1, 1});
-        }
-    };
-    for (auto& b : u->enc) add_block(b);
-    for (auto& b : u->dec) add_block(b);
-    u->c_total = coff;
-    add_param(u, "out_conv.weight", {c.out_channels, u->final_c, 3, 3});
-    for (auto& b : u->enc) if (!b.is_conv && (b.cout % 64 || b.cin % 64)) return fail(TD_ERR_UNSUPPORTED, "block channels must be multiples of 64: " + b.name);
-    for (auto& b : u->dec) if (b.cout % 64 || b.cin % 64) return fail(TD_ERR_UNSUPPORTED, "block channels must be multiples of 64: " + b.name);
-    if (c.in_channels + 1 > 32) return fail(TD_ERR_UNSUPPORTED, "in_channels+1 must fit one K chunk (<=32)");
-    if (c.out_channels > 8) return fail(TD_ERR_UNSUPPORTED, "out_channels must be <= 8");
-    return TD_OK;
-}
-
-// The two stacks of the EDMAutoencoder as Block lists (edm_autoencoder.py:66-103; names are the reference's state-dict prefixes).  u->cfg carries the
-// stack's own channels: kind 1 in_channels -> 2 * latent_channels, kind 2 latent + direct channels -> out_channels.  No embedding parameters; the
-// reference's unused `emb_gain` scalars are not expected.
-static int build_blocks_ae(td_unet* u) {
-    const td_unet_config& c = u->cfg;
-    if (c.n_levels < 1 || c.n_levels > 8) return fail(TD_ERR_ARG, "n_levels out of range");
-    auto has_attn = [&](int res) { for (int i = 0; i < c.n_attn_resolutions; ++i) if (c.attn_resolutions[i] == res) return true; return false; };
-    u->emb_ch = 0; u->noise_dims = 0; u->c_total = 0;
-    int cout = c.in_channels + 1;
-    if (u->kind == 1) {   // edm_unet.py:107-121, encode_only
-        u->out_label = "encoder.out_conv"; u->out_gain_name = "encoder.out_gain";
-        for (int l = 0; l < c.n_levels; ++l) {
-            int ch = c.model_channels * c.channel_mults[l], res = c.image_size >> l;
-            std::string r = "encoder.enc." + std::to_string(res) + "x" + std::to_string(res);
-            Block b;
-            if (l == 0) { b.name = r + "_conv"; b.is_conv = true; b.cin = cout; b.cout = ch; cout = ch; }
-            else { b.name = r + "_down"; b.cin = cout; b.cout = cout; b.resample = 1; }
-            u->enc.push_back(b);
-            for (int i = 0; i < c.layers_per_block[l]; ++i) {
-                Block k;
-                k.name = r + "_block" + std::to_string(i);
-                k.cin = cout; k.cout = ch; k.attn = has_attn(res); cout = ch;
-                u->enc.push_back(k);
-            }
-        }
-    } else {              // edm_autoencoder.py:87-101
-        const int c0 = c.model_channels * c.channel_mults[c.n_levels - 1];
-        add_param(u, "decoder_conv.weight", {c0, cout, 1, 1});
-        cout = c0;
-        int idx = 0;
-        auto push = [&](int cin_, int cout_, int resample, bool attn) {
-            Block k;
-            k.name = "decoder." + std::to_string(idx++);
-            k.enc = false; k.cin = cin_; k.cout = cout_; k.resample = resample; k.attn = attn;
-            u->dec.push_back(k);
-        };
-        for (int l = c.n_levels - 1; l >= 0; --l) {
-            int ch = c.model_channels * c.channel_mults[l], res = c.image_size >> l;
-            if (l == c.n_levels - 1) { push(cout, cout, 0, c.midblock_attention != 0); push(cout, cout, 0, false); }
-            else push(cout, cout, 2, false);
-            for (int i = 0; i < u->lpb_dec[l] + 1; ++i) { push(cout, ch, 0, has_attn(res)); cout = ch; }
-        }
-    }
-    u->final_c = cout;
-    auto add_block = [&](Block& b) {
-        if (b.is_conv) { add_param(u, b.name + ".weight", {b.cout, b.cin, 3, 3}); return; }
-        b.cvec_off = 0;
-        add_param(u, b.name + ".conv_res0.weight", {b.cout, b.enc ? b.cout : b.cin, 3, 3});
-        add_param(u, b.name + ".conv_res1.weight", {b.cout, b.cout, 3, 3});
-        if (b.cin != b.cout) add_param(u, b.name + ".conv_skip.weight", {b.cout, b.cin, 1, 1});
-        if (b.attn) {
-            add_param(u, b.name + ".attn_qkv.weight", {3 * b.cout, b.cout, 1, 1});
-            add_param(u, b.name + ".attn_proj.weight", {b.cout, b.cout, 1, 1});
-        }
-    };
-    for (auto& b : u->enc) add_block(b);
-    for (auto& b : u->dec) add_block(b);
-    add_param(u, u->out_label + ".weight", {c.out_channels, u->final_c, 3, 3});
-    add_param(u, u->out_gain_name, {});
-    for (auto& b : u->enc) if (!b.is_conv && (b.cout % 64 || b.cin % 64)) return fail(TD_ERR_UNSUPPORTED, "block channels must be multiples of 64: " + b.name);
-    for (auto& b : u->dec) if (b.cout % 64 || b.cin % 64) return fail(TD_ERR_UNSUPPORTED, "block channels must be multiples of 64: " + b.name);
     return TD_OK;
 }
 
@@ -607,25 +443,16 @@ static int ensure_packed_s16(td_unet* u, ConvWeights& cw) {
     return TD_OK;
 }
 
-static const float kMixRes = 0.7f / 0.76157731058639082f;   // (1-0.3)/sqrt(0.7^2+0.3^2)
-static const float kMixNew = 0.3f / 0.76157731058639082f;
-
 static int finalize(td_unet* u) {
     for (auto& p : u->params) if (!p.set) return fail(TD_ERR_STATE, "parameter not set: " + p.name);
-    const int chunk = u->chunk;
     auto folded = [&](const std::string& n, float gain) -> const std::vector<float>* {
         auto& v = u->folded[n];
         if (v.empty()) fold(P(u, n), gain, v, u->prefolded);
         return &v;
     };
-    auto pad = [&](int c) { return (c + chunk - 1) / chunk * chunk; };
-    const float out_gain = P(u, u->out_gain_name).data[0];
     int rc;
     if (u->kind != 0) {   // no embedding: one row of ones serves every block and every image (+ slack for the epilogues' 16-byte row reads)
-        int max_cout = 64;
-        for (auto& b : u->enc) max_cout = std::max(max_cout, b.cout);
-        for (auto& b : u->dec) max_cout = std::max(max_cout, b.cout);
-        std::vector<float> ones((size_t)max_cout + 256, 1.f);
+        std::vector<float> ones((size_t)u->g.max_cout + 256, 1.f);
         u->d_ones.reset(new DevBuf());
         HIP_TRY(u->d_ones->alloc(ones.size() * 4, false));
         HIP_TRY(hipMemcpy(u->d_ones->p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice));
@@ -669,14 +496,14 @@ static int finalize(td_unet* u) {
         }
         std::vector<float> wall;
         std::vector<int> woff, coff, cout;
-        auto add = [&](const Block& b) {
+        auto add = [&](const GraphBlock& b) {
             if (b.is_conv) return;
             const std::vector<float>* w = folded(b.name + ".emb_linear.weight", P(u, b.name + ".emb_gain").data[0]);
             woff.push_back((int)wall.size()); coff.push_back(b.cvec_off); cout.push_back(b.cout);
             wall.insert(wall.end(), w->begin(), w->end());
         };
-        for (auto& b : u->enc) add(b);
-        for (auto& b : u->dec) add(b);
+        for (auto& b : u->g.enc) add(b);
+        for (auto& b : u->g.dec) add(b);
         u->n_blocks = (int)woff.size();
         if ((rc = up(u->d_wemb, wall))) return rc;
         auto upi = [&](Buf& b, const std::vector<int>& v) -> int {
@@ -687,55 +514,22 @@ static int finalize(td_unet* u) {
         };
         if ((rc = upi(u->d_blk_woff, woff)) || (rc = upi(u->d_blk_coff, coff)) || (rc = upi(u->d_blk_cout, cout))) return rc;
     }
-    // conv weights per fused op
-    auto mk = [&](const std::string& label, int cout_, std::vector<WSeg> segs) -> int {
-        ConvWeights& cw = u->convw[label];
-        cw.cout = cout_; cw.segs = std::move(segs);
-        return pack_conv(u, cw);
-    };
-    auto seg = [&](const std::string& wname, float gain, int cin_tot, int cin_off, int c, int taps, float mul) {
-        WSeg s; s.w = folded(wname, gain); s.cin_tot = cin_tot; s.cin_off = cin_off; s.c_real = c; s.c_pad = pad(c); s.taps = taps; s.mul = mul; return s;
-    };
-    const float t = u->cfg.concat_balance;
-    auto do_block = [&](const Block& b) -> int {
-        const std::string& n = b.name;
-        if (b.is_conv) return mk(n, b.cout, {seg(n + ".weight", 1.f, b.cin, 0, b.cin, 9, 1.f)});
-        if (b.enc) {
-            if (b.cin != b.cout && (rc = mk(n + ".conv_skip", b.cout, {seg(n + ".conv_skip.weight", 1.f, b.cin, 0, b.cin, 1, 1.f)}))) return rc;
-            if ((rc = mk(n + ".conv_res0", b.cout, {seg(n + ".conv_res0.weight", 1.f, b.cout, 0, b.cout, 9, 1.f)}))) return rc;
-            if ((rc = mk(n + ".conv_res1", b.cout, {seg(n + ".conv_res1.weight", 1.f, b.cout, 0, b.cout, 9, kMixNew)}))) return rc;
-        } else {
-            const int cx = b.cin - b.skip_c;
-            float sa = 1.f, sb = 1.f;
-            if (b.concat) {  // mp_concat([x, skip], w=[1-t, t]) — mp_layers.py:65-86
-                double wa = 1.0 - t, wb = t, C = sqrt((double)b.cin / (wa * wa + wb * wb));
-                sa = (float)(C / sqrt((double)cx) * wa); sb = (float)(C / sqrt((double)b.skip_c) * wb);
-            }
-            std::vector<WSeg> s0;
-            s0.push_back(seg(n + ".conv_res0.weight", 1.f, b.cin, 0, cx, 9, 1.f));
-            if (b.concat) s0.push_back(seg(n + ".conv_res0.weight", 1.f, b.cin, cx, b.skip_c, 9, 1.f));
-            if ((rc = mk(n + ".conv_res0", b.cout, s0))) return rc;
-            std::vector<WSeg> s1;
-            s1.push_back(seg(n + ".conv_res1.weight", 1.f, b.cout, 0, b.cout, 9, kMixNew));
-            if (b.cin != b.cout) {  // 1x1 skip conv over the mp_concat'ed input, fused as extra K segments
-                s1.push_back(seg(n + ".conv_skip.weight", 1.f, b.cin, 0, cx, 1, kMixRes * sa));
-                if (b.concat) s1.push_back(seg(n + ".conv_skip.weight", 1.f, b.cin, cx, b.skip_c, 1, kMixRes * sb));
-            }
-            if ((rc = mk(n + ".conv_res1", b.cout, s1))) return rc;
+    // conv weights per fused op: the weight side of the graph's K-segments
+    u->convw.clear();
+    u->convw.resize(u->g.ops.size());
+    for (size_t i = 0; i < u->g.ops.size(); ++i) {
+        const GraphOp& gop = u->g.ops[i];
+        if (gop.attn) continue;
+        ConvWeights& cw = u->convw[i];
+        cw.cout = gop.cout;
+        for (const GraphSeg& gs : gop.segs) {
+            WSeg s;
+            static_cast<GraphSeg&>(s) = gs;
+            s.w = folded(gs.wname, gs.gain.empty() ? 1.f : P(u, gs.gain).data[0]);
+            cw.segs.push_back(s);
         }
-        if (b.attn) {
-            if ((rc = mk(n + ".attn_qkv", 3 * b.cout, {seg(n + ".attn_qkv.weight", 1.f, b.cout, 0, b.cout, 1, 1.f)}))) return rc;
-            if ((rc = mk(n + ".attn_proj", b.cout, {seg(n + ".attn_proj.weight", 1.f, b.cout, 0, b.cout, 1, kMixNew)}))) return rc;
-        }
-        return TD_OK;
-    };
-    if (u->kind == 2) {   // decoder_conv: 1x1 over latent + direct + ones channels (edm_autoencoder.py:89,137-138)
-        const int cin = u->cfg.in_channels + 1, c0 = u->dec.front().cin;
-        if ((rc = mk("decoder_conv", c0, {seg("decoder_conv.weight", 1.f, cin, 0, cin, 1, 1.f)}))) return rc;
+        if ((rc = pack_conv(u, cw))) return rc;
     }
-    for (auto& b : u->enc) if ((rc = do_block(b))) return rc;
-    for (auto& b : u->dec) if ((rc = do_block(b))) return rc;
-    if ((rc = mk(u->out_label, u->cfg.out_channels, {seg(u->out_label + ".weight", out_gain, u->final_c, 0, u->final_c, 9, 1.f)}))) return rc;
     for (auto& p : u->params) { p.data.clear(); p.data.shrink_to_fit(); }
     u->folded.clear();
     HIP_TRY(hipDeviceSynchronize());
@@ -752,8 +546,6 @@ static int new_buf(Plan& pl, size_t bytes, void** out) {
     pl.bufs.push_back(std::move(b));
     return TD_OK;
 }
-
-struct SegSpec { const Tensor* t; int C; int taps; int resample; int xform; float scale; };
 
 // The plan options (conv_select.h: PlanOptions) with the defaults that ship.  These are the ONLY read sites of plan options: the plan builder and the
 // conv selector work on the struct, and build_plan makes the plan-cache key from its members.
@@ -835,6 +627,8 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
     const int chunk = u->chunk;
     int rc;
     size_t partial_bytes = 0;
+    std::vector<Tensor> T(u->g.tensors.size());   // the graph's tensors at this shape
+    auto dim = [](int v, int level) { for (; level > 0; --level) v = (v + 1) / 2; for (; level < 0; ++level) v *= 2; return v; };   // map size at a level
 
     auto new_tensor = [&](int C, int h, int w, bool want_sumsq, int nparts, Tensor* t) -> int {
         t->C = C; t->cstride = C; t->H = h; t->W = w; t->sumsq = nullptr; t->nparts = 0;
@@ -847,33 +641,33 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         return TD_OK;
     };
 
-    // emits one fused conv op: wires its segments, lets conv_select choose kernel / tile / split-K, allocates its output (unless out_f32 target given)
-    auto conv = [&](const std::string& label, std::vector<SegSpec> segs, int h, int w, int epi, int cvec_off, const Tensor* res, int res_resample,
-                    bool res_norm, float clip, bool want_sumsq, bool out_f32, Tensor* outT) -> int {
-        auto wit = u->convw.find(label);
-        if (wit == u->convw.end()) return fail(TD_ERR_STATE, "no weights for " + label);
-        ConvWeights& cw = wit->second;
+    // emits one fused conv op of the graph: wires the activation side of its segments, lets conv_select choose kernel / tile / split-K, allocates its output
+    auto conv = [&](const GraphOp& g, ConvWeights& cw) -> int {
+        const std::string& label = g.label;
+        const int h = dim(H, g.level), w = dim(W, g.level);
+        const Tensor* res = g.res >= 0 ? &T[g.res] : nullptr;
+        Tensor* outT = &T[g.out];
         Op op;
         op.label = label;
         ConvParams& p = op.p;
         memset(&p, 0, sizeof p);
-        p.nseg = (int)segs.size();
+        p.nseg = (int)g.segs.size();
         int kgroups = 0;
         for (int i = 0; i < p.nseg; ++i) {
-            const SegSpec& s = segs[i];
+            const GraphSeg& s = g.segs[i];
+            const Tensor* st = &T[s.src];
             ConvSeg& d = p.seg[i];
-            d.src = s.t->ptr; d.C = (s.C + chunk - 1) / chunk * chunk; d.cstride = s.t->cstride; d.Hs = s.t->H; d.Ws = s.t->W;
+            d.src = st->ptr; d.C = s.c_pad; d.cstride = st->cstride; d.Hs = st->H; d.Ws = st->W;
             // the kernels address activations with 32-bit element offsets (pixel * channel stride): refuse instead of wrapping around
             if ((size_t)N * d.Hs * d.Ws * (size_t)d.cstride >= ((size_t)1 << 31))
                 return fail(TD_ERR_ARG, "batch too large for 32-bit activation addressing (N*H*W*C >= 2^31 elements in " + label + "): split the batch");
             d.taps = s.taps; d.resample = s.resample; d.xform = s.xform; d.scale = s.scale;
             if (s.xform == 2) {
-                if (!s.t->sumsq) return fail(TD_ERR_STATE, "pixel-norm source without sumsq: " + label);
-                d.sumsq = s.t->sumsq; d.nparts = s.t->nparts; d.inv_c = 1.f / (float)s.t->C;
+                if (!st->sumsq) return fail(TD_ERR_STATE, "pixel-norm source without sumsq: " + label);
+                d.sumsq = st->sumsq; d.nparts = st->nparts; d.inv_c = 1.f / (float)st->C;
             }
             kgroups += d.C / chunk;
-            op.k_alg += (double)cw.segs[i].c_real * s.taps;   // e.g. 6 of the input conv's 64 padded channels
-            if (cw.segs[i].c_pad != d.C || cw.segs[i].taps != d.taps) return fail(TD_ERR_STATE, "segment/weight mismatch: " + label);
+            op.k_alg += (double)s.c_real * s.taps;   // e.g. 6 of the input conv's 64 padded channels
         }
         p.wpack = cw.packed->p;
         p.N = N; p.H = h; p.W = w; p.Cout = cw.cout; p.CoutPad = cw.cout_pad; p.kgroups = kgroups;
@@ -881,7 +675,7 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         ConvSelIn in;
         in.N = N; in.h = h; in.w = w; in.cout = cw.cout; in.cout_pad = cw.cout_pad; in.kgroups = kgroups; in.nseg = p.nseg;
         for (int i = 0; i < p.nseg; ++i) in.seg[i] = {p.seg[i].C, p.seg[i].taps, p.seg[i].xform, p.seg[i].resample, p.seg[i].Hs, p.seg[i].Ws};
-        in.chunk = chunk; in.dt = u->dt; in.bf16 = u->bf16; in.sb_n3 = cw.sb_n3; in.out_f32 = out_f32; in.epi = epi; in.has_res = res != nullptr; in.clip_pos = clip > 0.f;
+        in.chunk = chunk; in.dt = u->dt; in.bf16 = u->bf16; in.sb_n3 = cw.sb_n3; in.out_f32 = g.out_f32; in.epi = g.epi; in.has_res = res != nullptr; in.clip_pos = g.clip > 0.f;
         in.n_cus = u->eng->n_cus; in.op_index = (int)pl.ops.size();
         const ConvSel& sel = op.sel = conv_select(in, po);
         p.tiles_x = sel.tiles_x; p.tiles_y = sel.tiles_y; p.img_groups = sel.img_groups; p.n_ntiles = sel.n_ntiles; p.ksplit = sel.ksplit;
@@ -889,19 +683,19 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
         if (sel.wcopy == ConvWeightCopy::Sb) { if ((rc = ensure_packed_sb(u, cw))) return rc; p.wpack_sb = cw.packed_sb->p; p.sb_n3 = cw.sb_n3; }
         if (sel.wcopy == ConvWeightCopy::S16) { if ((rc = ensure_packed_s16(u, cw))) return rc; p.wpack_sb = cw.packed_s16->p; p.sb_n3 = cw.sb_n3; }
         if (!conv_set_kbounds(p, po.splitk_weighted != 0, chunk)) return fail(TD_ERR_UNSUPPORTED, "split-K bounds: " + label);
-        p.epi = epi; p.out_f32 = out_f32 ? 1 : 0; p.clip = clip; p.zeros = u->eng->zeros;
-        if (out_f32) {
+        p.epi = g.epi; p.out_f32 = g.out_f32 ? 1 : 0; p.clip = g.clip; p.zeros = u->eng->zeros;
+        if (g.out_f32) {
             outT->C = cw.cout; outT->cstride = 8; outT->H = h; outT->W = w; outT->sumsq = nullptr;
             if ((rc = new_buf(pl, (size_t)N * h * w * 8 * 4, &outT->ptr))) return rc;
-        } else if ((rc = new_tensor(cw.cout, h, w, want_sumsq, sel.out_parts, outT))) return rc;
+        } else if ((rc = new_tensor(cw.cout, h, w, g.want_sumsq, sel.out_parts, outT))) return rc;
         p.out = outT->ptr; p.out_cstride = outT->cstride; p.out_sumsq = outT->sumsq;
         if ((size_t)N * h * w * (size_t)std::max(outT->cstride, cw.cout_pad) >= ((size_t)1 << 31))
             return fail(TD_ERR_ARG, "batch too large for 32-bit activation addressing (output of " + label + "): split the batch");
-        op.cvec_off = cvec_off; p.cvec_stride = u->c_total;
+        op.cvec_off = g.cvec_off; p.cvec_stride = u->g.c_total;
         if (res) {
-            p.res = res->ptr; p.res_cstride = res->cstride; p.res_Hs = res->H; p.res_Ws = res->W; p.res_resample = res_resample;
+            p.res = res->ptr; p.res_cstride = res->cstride; p.res_Hs = res->H; p.res_Ws = res->W; p.res_resample = g.res_resample;
             p.res_scale = kMixRes;
-            if (res_norm) {
+            if (g.res_norm) {
                 if (!res->sumsq) return fail(TD_ERR_STATE, "normed residual without sumsq: " + label);
                 p.res_sumsq = res->sumsq; p.res_nparts = res->nparts; p.res_inv_c = 1.f / (float)res->C;
             }
@@ -934,89 +728,25 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
     };
 
     // input tensor (ones channel appended, zero padded to one K chunk)
-    Tensor xin;
+    Tensor& xin = T[0];
     xin.C = chunk; xin.cstride = chunk; xin.H = H; xin.W = W;
     if ((rc = new_buf(pl, (size_t)N * H * W * chunk * es, &xin.ptr))) return rc;
     pl.xin = xin.ptr;
 
-    std::vector<Tensor> skips;
-    Tensor cur = xin;
-    int h = H, w = W;
-    if (u->kind == 2) {
-        Tensor o;
-        if ((rc = conv("decoder_conv", {{&cur, chunk, 1, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, false, &o))) return rc;
-        cur = o;
-    }
-    for (size_t bi = 0; bi < u->enc.size(); ++bi) {
-        const Block& b = u->enc[bi];
-        // does the consumer of this block's output pixel-normalise it directly (enc block without skip conv)?
-        bool next_norms = bi + 1 < u->enc.size() && u->enc[bi + 1].cin == u->enc[bi + 1].cout;
-        Tensor o;
-        if (b.is_conv) {
-            if ((rc = conv(b.name, {{&cur, chunk, 9, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, next_norms, false, &o))) return rc;
-        } else {
-            if (b.resample == 1) { h = (h + 1) / 2; w = (w + 1) / 2; }
-            Tensor xs = cur;
-            int rs = b.resample;
-            if (b.cin != b.cout) {
-                if ((rc = conv(b.name + ".conv_skip", {{&cur, b.cin, 1, rs, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, true, false, &xs))) return rc;
-                rs = 0;
-            }
-            Tensor y1;
-            if ((rc = conv(b.name + ".conv_res0", {{&xs, b.cout, 9, rs, 2, 1.f}}, h, w, EPI_EMB_SILU, b.cvec_off, nullptr, 0, false, 0.f, false, false, &y1))) return rc;
-            if ((rc = conv(b.name + ".conv_res1", {{&y1, b.cout, 9, 0, 0, 1.f}}, h, w, EPI_RESIDUAL, -1, &xs, rs, true, b.attn ? 0.f : 256.f, next_norms && !b.attn, false, &o))) return rc;
-            if (b.attn) {
-                if ((rc = attn_fits(h * w, b.name))) return rc;
-                Tensor qkv, att, o2;
-                if ((rc = conv(b.name + ".attn_qkv", {{&o, b.cout, 1, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, false, &qkv))) return rc;
-                if ((rc = new_tensor(b.cout, h, w, false, 0, &att))) return rc;
-                Op a; a.kind = Op::ATTN; a.qkv = qkv.ptr; a.att = att.ptr; a.tokens = h * w; a.C = b.cout; a.label = b.name + ".attn"; a.out_C = b.cout; a.out_H = h; a.out_W = w;
-                if ((rc = attn_workspace(a))) return rc;
-                pl.ops.push_back(a);
-                if ((rc = conv(b.name + ".attn_proj", {{&att, b.cout, 1, 0, 0, 1.f}}, h, w, EPI_RESIDUAL, -1, &o, 0, false, 256.f, next_norms, false, &o2))) return rc;
-                o = o2;
-            }
+    for (size_t i = 0; i < u->g.ops.size(); ++i) {
+        const GraphOp& g = u->g.ops[i];
+        const int h = dim(H, g.level), w = dim(W, g.level);
+        if (!g.attn) {
+            if (i + 1 < u->g.ops.size() && u->g.ops[i + 1].attn && (rc = attn_fits(h * w, u->g.ops[i + 1].block))) return rc;   // before its qkv conv allocates
+            if ((rc = conv(g, u->convw[i]))) return rc;
+            continue;
         }
-        cur = o;
-        skips.push_back(o);
+        if ((rc = new_tensor(g.cout, h, w, false, 0, &T[g.out]))) return rc;
+        Op a; a.kind = Op::ATTN; a.qkv = T[g.qkv].ptr; a.att = T[g.out].ptr; a.tokens = h * w; a.C = g.cout; a.label = g.label; a.out_C = g.cout; a.out_H = h; a.out_W = w;
+        if ((rc = attn_workspace(a))) return rc;
+        pl.ops.push_back(a);
     }
-    for (const Block& b : u->dec) {
-        Tensor skip;
-        if (b.concat) { skip = skips.back(); skips.pop_back(); }
-        if (b.resample == 2) { h *= 2; w *= 2; }
-        const int cx = b.cin - b.skip_c;
-        float sa = 1.f, sb = 1.f;
-        if (b.concat) {
-            double t = u->cfg.concat_balance, wa = 1.0 - t, wb = t, C = sqrt((double)b.cin / (wa * wa + wb * wb));
-            sa = (float)(C / sqrt((double)cx) * wa); sb = (float)(C / sqrt((double)b.skip_c) * wb);
-        }
-        std::vector<SegSpec> s0 = {{&cur, cx, 9, b.resample, 1, sa}};
-        if (b.concat) s0.push_back({&skip, b.skip_c, 9, 0, 1, sb});
-        Tensor y1, o;
-        if ((rc = conv(b.name + ".conv_res0", s0, h, w, EPI_EMB_SILU, b.cvec_off, nullptr, 0, false, 0.f, false, false, &y1))) return rc;
-        std::vector<SegSpec> s1 = {{&y1, b.cout, 9, 0, 0, 1.f}};
-        const Tensor* res = nullptr;
-        if (b.cin != b.cout) {
-            s1.push_back({&cur, cx, 1, b.resample, 0, 1.f});
-            if (b.concat) s1.push_back({&skip, b.skip_c, 1, 0, 0, 1.f});
-        } else res = &cur;
-        if ((rc = conv(b.name + ".conv_res1", s1, h, w, EPI_RESIDUAL, -1, res, b.resample, false, b.attn ? 0.f : 256.f, false, false, &o))) return rc;
-        if (b.attn) {
-            if ((rc = attn_fits(h * w, b.name))) return rc;
-            Tensor qkv, att, o2;
-            if ((rc = conv(b.name + ".attn_qkv", {{&o, b.cout, 1, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, false, &qkv))) return rc;
-            if ((rc = new_tensor(b.cout, h, w, false, 0, &att))) return rc;
-            Op a; a.kind = Op::ATTN; a.qkv = qkv.ptr; a.att = att.ptr; a.tokens = h * w; a.C = b.cout; a.label = b.name + ".attn"; a.out_C = b.cout; a.out_H = h; a.out_W = w;
-            if ((rc = attn_workspace(a))) return rc;
-            pl.ops.push_back(a);
-            if ((rc = conv(b.name + ".attn_proj", {{&att, b.cout, 1, 0, 0, 1.f}}, h, w, EPI_RESIDUAL, -1, &o, 0, false, 256.f, false, false, &o2))) return rc;
-            o = o2;
-        }
-        cur = o;
-    }
-    Tensor Ft;
-    if ((rc = conv(u->out_label, {{&cur, u->final_c, 9, 0, 0, 1.f}}, h, w, EPI_PLAIN, -1, nullptr, 0, false, 0.f, false, true, &Ft))) return rc;
-    pl.F = (float*)Ft.ptr;
+    pl.F = (float*)T[u->g.ops.back().out].ptr;
     // Producer-side activation: a segment that takes mp_silu(scale * x) of a whole conv output (decoder blocks: the running tensor
     // and the skip tensor of the concatenation) reads a second copy that the PRODUCER's epilogue writes already activated, instead of
     // applying exp/rcp to every 16-byte piece of every halo patch in every cout-tile workgroup of the consumer.  One copy per
@@ -1070,38 +800,34 @@ static int compute_cvecs(td_unet* u, Plan& pl, const std::vector<float>& t_steps
         pl.drop_graph();
         HIP_TRY(hipStreamSynchronize(st));
         pl.emb.reset(new DevBuf()); pl.cvec.reset(new DevBuf()); pl.tsteps.reset(new DevBuf());
-        HIP_TRY(pl.emb->alloc((size_t)rows * u->emb_ch * 4));
-        HIP_TRY(pl.cvec->alloc((size_t)rows * u->c_total * 4));
+        HIP_TRY(pl.emb->alloc((size_t)rows * u->g.emb_ch * 4));
+        HIP_TRY(pl.cvec->alloc((size_t)rows * u->g.c_total * 4));
         HIP_TRY(pl.tsteps->alloc(std::max<size_t>(64, t_steps.size()) * 4));
         pl.cvec_rows = rows;
     }
     // `t_steps` lives on the caller's stack: with option "async" the call may return before the stream gets here, so the (80-byte) upload goes
     // through the engine's pinned ring
     { int rc_ = upload(u->eng, pl.tsteps->p, t_steps.data(), t_steps.size() * 4); if (rc_) return rc_; }
-    const int half = u->noise_dims / 2;
-    hipLaunchKernelGGL(emb_kernel, dim3(rows, (u->emb_ch + 63) / 64), dim3(256), (size_t)(2 * half + u->embd.feat_total) * 4, st, (const float*)pl.tsteps->p, d_cond, pl.N,
+    const int half = u->g.noise_dims / 2;
+    hipLaunchKernelGGL(emb_kernel, dim3(rows, (u->g.emb_ch + 63) / 64), dim3(256), (size_t)(2 * half + u->embd.feat_total) * 4, st, (const float*)pl.tsteps->p, d_cond, pl.N,
                        (const float*)u->d_freqs->p, half, (const float*)u->d_wnoise->p, (const float*)u->d_wcond->p, (const float*)u->d_fourier->p,
-                       u->embd, u->emb_ch, (float*)pl.emb->p);
-    int max_cout = 64;
-    for (auto& b : u->enc) max_cout = std::max(max_cout, b.cout);
-    for (auto& b : u->dec) max_cout = std::max(max_cout, b.cout);
-    bool c16 = u->emb_ch % 16 == 0 && u->c_total % 4 == 0;   // the matrix-core form needs 16-byte operand pieces and whole 16-cout slices
-    for (auto& b : u->enc) c16 = c16 && b.cout % 16 == 0;
-    for (auto& b : u->dec) c16 = c16 && b.cout % 16 == 0;
-    if (c16 && u->emb_ch % 64 == 0)
+                       u->embd, u->g.emb_ch, (float*)pl.emb->p);
+    const int max_cout = u->g.max_cout;
+    const bool c16 = u->g.emb_ch % 16 == 0 && u->g.c_total % 4 == 0 && u->g.cout16;   // the matrix-core form needs 16-byte operand pieces and whole 16-cout slices
+    if (c16 && u->g.emb_ch % 64 == 0)
         hipLaunchKernelGGL(cvec_mfma_kernel<4>, dim3((max_cout + 63) / 64, (rows + 63) / 64, u->n_blocks), dim3(256), 0, st, (const float*)pl.emb->p, rows,
-                           u->emb_ch, (const float*)u->d_wemb->p, (const int*)u->d_blk_woff->p, (const int*)u->d_blk_coff->p, (const int*)u->d_blk_cout->p,
-                           u->c_total, (float*)pl.cvec->p);
+                           u->g.emb_ch, (const float*)u->d_wemb->p, (const int*)u->d_blk_woff->p, (const int*)u->d_blk_coff->p, (const int*)u->d_blk_cout->p,
+                           u->g.c_total, (float*)pl.cvec->p);
     else if (c16)
         hipLaunchKernelGGL(cvec_mfma_kernel<1>, dim3((max_cout + 63) / 64, (rows + 63) / 64, u->n_blocks), dim3(256), 0, st, (const float*)pl.emb->p, rows,
-                           u->emb_ch, (const float*)u->d_wemb->p, (const int*)u->d_blk_woff->p, (const int*)u->d_blk_coff->p, (const int*)u->d_blk_cout->p,
-                           u->c_total, (float*)pl.cvec->p);
+                           u->g.emb_ch, (const float*)u->d_wemb->p, (const int*)u->d_blk_woff->p, (const int*)u->d_blk_coff->p, (const int*)u->d_blk_cout->p,
+                           u->g.c_total, (float*)pl.cvec->p);
     else
-    hipLaunchKernelGGL(cvec_kernel, dim3((max_cout + 63) / 64, (rows + 15) / 16, u->n_blocks), dim3(256), (size_t)16 * u->emb_ch * 4, st, (const float*)pl.emb->p, rows,
-                       u->emb_ch, (const float*)u->d_wemb->p, (const int*)u->d_blk_woff->p, (const int*)u->d_blk_coff->p, (const int*)u->d_blk_cout->p,
-                       u->c_total, (float*)pl.cvec->p);
+    hipLaunchKernelGGL(cvec_kernel, dim3((max_cout + 63) / 64, (rows + 15) / 16, u->n_blocks), dim3(256), (size_t)16 * u->g.emb_ch * 4, st, (const float*)pl.emb->p, rows,
+                       u->g.emb_ch, (const float*)u->d_wemb->p, (const int*)u->d_blk_woff->p, (const int*)u->d_blk_coff->p, (const int*)u->d_blk_cout->p,
+                       u->g.c_total, (float*)pl.cvec->p);
     hipLaunchKernelGGL(cvec_norm_kernel, dim3(rows, u->n_blocks), dim3(256), 0, st, (float*)pl.cvec->p, (const int*)u->d_blk_coff->p,
-                       (const int*)u->d_blk_cout->p, u->c_total);
+                       (const int*)u->d_blk_cout->p, u->g.c_total);
     HIP_TRY(hipGetLastError());
     pl.cvec_written = rows;
     return TD_OK;
@@ -1124,7 +850,7 @@ static hipError_t launch_selected(const ConvParams& p, const ConvSel& s, int dt,
 // `fuse` (EDM sampler): the output conv runs the DPM-Solver++ update of this step in its epilogue (EPI_DPM_STEP) instead of writing F
 static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = nullptr) {
     hipStream_t st = u->eng->stream;
-    const float* cbase = u->kind != 0 ? (const float*)u->d_ones->p : (const float*)pl.cvec->p + (size_t)step * pl.N * u->c_total;
+    const float* cbase = u->kind != 0 ? (const float*)u->d_ones->p : (const float*)pl.cvec->p + (size_t)step * pl.N * u->g.c_total;
     const bool prof = u->eng->option("profile", 0) != 0;
     std::vector<hipEvent_t> evs;
     std::vector<int> ev_kind;
@@ -1302,7 +1028,7 @@ int td_unet_create(td_engine* e, const td_unet_config* cfg, int dtype, td_unet**
     if (dtype != TD_DTYPE_F32 && dtype != TD_DTYPE_BF16 && dtype != TD_DTYPE_F16) return fail(TD_ERR_ARG, "dtype");
     std::unique_ptr<td_unet> u(new td_unet());
     u->eng = e; u->cfg = *cfg; u->dt = dtype; u->bf16 = dtype != TD_DTYPE_F32; u->chunk = u->bf16 ? 64 : 32;
-    int rc = build_blocks(u.get());
+    int rc = init_graph(u.get(), nullptr);
     if (rc) return rc;
     *out = u.release();
     return TD_OK;
@@ -1369,9 +1095,9 @@ int td_unet_forward(td_unet* u, int n, int H, int W, const float* x, const float
         // rows = n "steps" x n tiles; sample i uses row i*n + i.  Build a compact [n][c_total] table by copying those rows to step 0's slot.
         if ((rc = compute_cvecs(u, *pl, ts, (const float*)dcond))) return rc;
         for (int i = 1; i < n; ++i) {
-            HIP_TRY(hipMemcpyAsync((float*)pl->cvec->p + (size_t)i * u->c_total, (float*)pl->cvec->p + ((size_t)i * n + i) * u->c_total, (size_t)u->c_total * 4,
+            HIP_TRY(hipMemcpyAsync((float*)pl->cvec->p + (size_t)i * u->g.c_total, (float*)pl->cvec->p + ((size_t)i * n + i) * u->g.c_total, (size_t)u->g.c_total * 4,
                                    hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync((float*)pl->emb->p + (size_t)i * u->emb_ch, (float*)pl->emb->p + ((size_t)i * n + i) * u->emb_ch, (size_t)u->emb_ch * 4,
+            HIP_TRY(hipMemcpyAsync((float*)pl->emb->p + (size_t)i * u->g.emb_ch, (float*)pl->emb->p + ((size_t)i * n + i) * u->g.emb_ch, (size_t)u->g.emb_ch * 4,
                                    hipMemcpyDeviceToDevice, st));
         }
     }
@@ -1391,7 +1117,7 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
     if (rc) return rc;
     if (!strcmp(label, "@emb") || !strcmp(label, "@cvec")) {
         const bool is_emb = !strcmp(label, "@emb");
-        const int width = is_emb ? u->emb_ch : u->c_total;
+        const int width = is_emb ? u->g.emb_ch : u->g.c_total;
         dims[0] = n; dims[1] = width; dims[2] = 1; dims[3] = 1;
         if ((int64_t)n * width > capacity) return fail(TD_ERR_ARG, "capacity");
         HIP_TRY(hipStreamSynchronize(u->eng->stream));
@@ -1401,7 +1127,7 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
     if (!strcmp(label, "@emb:rows") || !strcmp(label, "@cvec:rows")) {
         // every (step, tile) row the last compute_cvecs on this plan wrote, not only the first n
         const bool is_emb = !strcmp(label, "@emb:rows");
-        const int width = is_emb ? u->emb_ch : u->c_total, rows = pl->cvec_written;
+        const int width = is_emb ? u->g.emb_ch : u->g.c_total, rows = pl->cvec_written;
         if (rows < 1 || !pl->emb) return fail(TD_ERR_STATE, "no embedding rows on this plan yet: run a forward or a sampler call first");
         dims[0] = rows; dims[1] = width; dims[2] = 1; dims[3] = 1;
         if ((int64_t)rows * width > capacity) return fail(TD_ERR_ARG, "capacity");
@@ -2309,12 +2035,12 @@ int td_ae_create(td_engine* e, const td_ae_config* cfg, int dtype, td_ae** out) 
         u->cfg.image_size = c.image_size; u->cfg.model_channels = c.model_channels; u->cfg.n_levels = c.n_levels;
         u->cfg.in_channels = kind == 1 ? c.in_channels : L + D;
         u->cfg.out_channels = kind == 1 ? 2 * L : c.out_channels;
-        for (int l = 0; l < c.n_levels; ++l) { u->cfg.channel_mults[l] = c.channel_mults[l]; u->cfg.layers_per_block[l] = c.layers_per_block[l]; u->lpb_dec[l] = c.layers_per_block_decoder[l]; }
+        for (int l = 0; l < c.n_levels; ++l) { u->cfg.channel_mults[l] = c.channel_mults[l]; u->cfg.layers_per_block[l] = c.layers_per_block[l]; }
         u->cfg.n_attn_resolutions = std::min(8, std::max(0, c.n_attn_resolutions));
         for (int i = 0; i < u->cfg.n_attn_resolutions; ++i) u->cfg.attn_resolutions[i] = c.attn_resolutions[i];
         u->cfg.midblock_attention = kind == 2 ? c.midblock_attention : 0;   // (the encoder has no mid block: edm_unet.py:128-129)
         u->cfg.concat_balance = 0.5f;
-        int rc = build_blocks_ae(u.get());
+        int rc = init_graph(u.get(), c.layers_per_block_decoder);
         if (rc) return rc;
         (kind == 1 ? a->enc : a->dec) = std::move(u);
     }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_select.h"   // EPI_*
+
 namespace td {
 
 // One K-segment of an implicit-GEMM convolution: a source activation tensor (NHWC), how it is
@@ -70,8 +72,6 @@ __device__ __forceinline__ T mul_then_cast(float a, float b) {
     asm("" : "+v"(p));
     return (T)p;
 }
-
-enum { EPI_PLAIN = 0, EPI_EMB_SILU = 1, EPI_RESIDUAL = 2, EPI_DPM_STEP = 3 };
 
 struct ConvParams {
     ConvSeg seg[3];
