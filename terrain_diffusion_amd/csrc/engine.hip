@@ -8,6 +8,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 #include <unordered_map>
 
@@ -196,53 +197,88 @@ static int upload(td_engine* e, void* dst, const void* src, size_t bytes) {
     return TD_OK;
 }
 
-// Stages a possibly-host input into device memory (returns device pointer, owning buffers appended to `hold`).
-static int to_device(td_engine* e, const void* src, size_t bytes, std::vector<Buf>& hold, const void** out) {
-    if (!src) { *out = nullptr; return TD_OK; }
-    if (is_device_ptr(src)) { *out = src; return TD_OK; }
-    Buf b(new DevBuf());
-    HIP_TRY(b->scratch(e->scratch, bytes));
-    { int rc_ = upload(e, b->p, src, bytes); if (rc_) return rc_; }
-    *out = b->p;
-    hold.push_back(std::move(b));
-    return TD_OK;
-}
-struct OutStage { void* dev; void* host; size_t bytes; };
-static int out_device(td_engine* e, void* dst, size_t bytes, std::vector<Buf>& hold, OutStage* st) {
-    st->host = nullptr; st->bytes = bytes;
-    if (is_device_ptr(dst)) { st->dev = dst; return TD_OK; }
-    Buf b(new DevBuf());
-    HIP_TRY(b->scratch(e->scratch, bytes));
-    st->dev = b->p; st->host = dst;
-    hold.push_back(std::move(b));
-    return TD_OK;
-}
-static int out_finish(td_engine* e, const OutStage& st) {
-    if (st.host) {
-        HIP_TRY(hipMemcpyAsync(st.host, st.dev, st.bytes, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
+// The scope of one C-ABI call: the device guard, the call's staging buffers, its host outputs and ONE flag -- "every caller buffer of this call is
+// device memory" -- from which finish() decides how the call ends.  An entry point names each caller pointer once, by what it is:
+//   in      a tensor that may be host or device            table    a small array the ABI defines as host (`*_host`, tap tables, descriptors)
+//   out     a result that may be host or device            inout    a host-or-device buffer updated in place
+//   direct  a pointer the entry point copies itself        scratch / keep   device memory that lives to the end of the call
+// Host arrays that uploads read (the job structs below) are declared BEFORE the Call, so that they outlive it: a call that returns without
+// finish() -- an error -- waits in the destructor for the uploads it enqueued before those arrays go.
+struct Call {
+    td_engine* const e;
+    DevGuard dg;
+    std::vector<Buf> hold;
+    struct HostOut { void* host; const void* dev; size_t bytes; };
+    std::vector<HostOut> outs;
+    bool all_device = true;   // no caller buffer of this call is host memory
+    bool uploaded = false;    // a copy from a host array has been enqueued
+    bool finished = false;
+    explicit Call(td_engine* e_) : e(e_), dg(e_->device) {}
+    ~Call() {
+        if (finished) return;
+        e->call_host_src = false;
+        if (uploaded) (void)hipStreamSynchronize(e->stream);
     }
-    return TD_OK;
-}
-
-// End of a C-ABI call.  Default: the call is synchronous (results complete on return).  With engine option "async" = 1 and only device
-// pointers involved, the work stays enqueued on e->stream -- typically the caller's own stream (td_engine_set_stream), so that it is ordered
-// with the caller's other GPU work without a host synchronisation -- and the call's staging buffers are parked until td_engine_synchronize.
-static int end_call(td_engine* e, std::vector<Buf>& hold, bool all_device) {
-    const bool host_src = e->call_host_src;
-    e->call_host_src = false;
-    if (all_device && !host_src && e->option("async", 0) != 0) {
-        // pooled scratch goes straight back to the pool (the stream orders its next use behind this call's work); buffers that would be
-        // hipFree'd -- which waits for the device -- are parked until the next synchronise
-        if (e->deferred.size() > 256) { HIP_TRY(hipStreamSynchronize(e->stream)); e->deferred.clear(); e->ring.reset(); }
-        for (auto& b : hold) if (b && !b->pool) e->deferred.push_back(std::move(b));
-        hold.clear();
+    void keep(Buf b) { hold.push_back(std::move(b)); }
+    template <typename T> int scratch(size_t bytes, T** p) {   // uninitialised
+        Buf b(new DevBuf());
+        HIP_TRY(b->scratch(e->scratch, bytes));
+        *p = (T*)b->p;
+        keep(std::move(b));
         return TD_OK;
     }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->ring.reset();
-    return TD_OK;
-}
+    int up(void* dst, const void* src, size_t bytes) { uploaded = true; return upload(e, dst, src, bytes); }
+    // does not mark the call: through the pinned ring it may still end enqueue-only (upload's call_host_src says when it may not)
+    template <typename T> int table(const T* src, size_t bytes, const T** dev) {
+        T* p;
+        int rc = scratch(bytes, &p);
+        *dev = p;
+        return rc ? rc : up(p, src, bytes);
+    }
+    template <typename T> int in(const T* src, size_t bytes, const T** dev) {
+        *dev = src;
+        if (direct(src)) return TD_OK;
+        return table(src, bytes, dev);
+    }
+    template <typename T> int out(T* dst, size_t bytes, T** dev) { return inout(dst, bytes, false, dev); }
+    // host: device scratch now (`read`: filled from the caller's buffer), copied back by finish
+    template <typename T> int inout(T* ptr, size_t bytes, bool read, T** dev) {
+        *dev = ptr;
+        if (direct(ptr)) return TD_OK;
+        int rc = scratch(bytes, dev);
+        if (rc) return rc;
+        outs.push_back({ptr, *dev, bytes});
+        if (read) { uploaded = true; HIP_TRY(hipMemcpyAsync(*dev, ptr, bytes, hipMemcpyHostToDevice, e->stream)); }
+        return TD_OK;
+    }
+    // residency of a caller pointer (NULL counts as device: nothing of the host is read through it)
+    bool direct(const void* p) {
+        const bool dev = !p || is_device_ptr(p);
+        all_device = all_device && dev;
+        return dev;
+    }
+    // End of the call: host outputs are copied back behind the work and the stream is waited for ONCE.  Default: the call is synchronous (results
+    // complete on return).  With engine option "async" = 1 and only device pointers involved, the work stays enqueued on e->stream -- typically the
+    // caller's own stream (td_engine_set_stream), so that it is ordered with the caller's other GPU work without a host synchronisation -- and the
+    // call's staging buffers are parked until td_engine_synchronize.  `always_sync`: the entry points that never honoured "async".
+    int finish(bool always_sync = false) {
+        for (const HostOut& o : outs) HIP_TRY(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, e->stream));
+        const bool host_src = e->call_host_src;
+        if (!always_sync && all_device && !host_src && e->option("async", 0) != 0) {
+            // pooled scratch goes straight back to the pool (the stream orders its next use behind this call's work); buffers that would be
+            // hipFree'd -- which waits for the device -- are parked until the next synchronise
+            if (e->deferred.size() > 256) { HIP_TRY(hipStreamSynchronize(e->stream)); e->deferred.clear(); e->ring.reset(); }
+            for (auto& b : hold) if (b && !b->pool) e->deferred.push_back(std::move(b));
+            hold.clear();
+        } else {
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            e->ring.reset();
+        }
+        e->call_host_src = false;
+        finished = true;
+        return TD_OK;
+    }
+};
 
 // ------------------------------------------------------------------------------------------------ model description
 struct Param : GraphParam {
@@ -287,6 +323,23 @@ struct Op {
     std::string label;
 };
 
+// Everything a captured EDM sampler graph has baked into its kernel arguments: the plan's graph is replayed only for a call with an equal key.
+struct GraphKey {
+    std::vector<float> sigmas;
+    float sigma_data = 0.f;
+    int solver_order = 0;
+    int lof = -1, fuse = -1, stop = -2;      // engine options "lower_order_final", "fuse_solver", "sampler_stop_after"
+    const void* guide = nullptr;             // guide plan / its modulation buffer / scale (autoguidance)
+    const void* guide_cvec = nullptr;
+    float gscale = 0.f;
+    float alpha = 1.f;                       // score-scaling factor and its (cos t_i, sin t_i) pairs
+    std::vector<float> cs;
+    bool operator==(const GraphKey& o) const {
+        return std::tie(sigmas, sigma_data, solver_order, lof, fuse, stop, guide, guide_cvec, gscale, alpha, cs) ==
+               std::tie(o.sigmas, o.sigma_data, o.solver_order, o.lof, o.fuse, o.stop, o.guide, o.guide_cvec, o.gscale, o.alpha, o.cs);
+    }
+};
+
 struct Plan {
     int N = 0, H = 0, W = 0;
     std::vector<Op> ops;
@@ -300,17 +353,7 @@ struct Plan {
     int cvec_written = 0;      // rows the last compute_cvecs wrote (read-back labels "@emb:rows" / "@cvec:rows")
     // graph cache for the EDM loop
     hipGraphExec_t graph = nullptr;
-    std::vector<float> graph_sigmas;
-    float graph_sigma_data = 0.f;
-    int graph_solver_order = 0;
-    int graph_lof = -1;        // engine option "lower_order_final" the graph was captured under
-    int graph_fuse = -1;       // engine option "fuse_solver" the graph was captured under
-    int graph_stop = -2;       // engine option "sampler_stop_after" the graph was captured under
-    const void* graph_guide = nullptr;       // guide plan / its modulation buffer / scale the captured graph was built with (autoguidance)
-    const void* graph_guide_cvec = nullptr;
-    float graph_gscale = 0.f;
-    float graph_alpha = 1.f;                 // score-scaling factor and the (cos t_i, sin t_i) pairs baked into the captured graph's kernel arguments
-    std::vector<float> graph_cs;
+    GraphKey graph_key;        // what `graph` was captured under
     size_t bytes = 0;          // device memory owned by this plan (activations, partials, sampler state)
     uint64_t last_use = 0;     // LRU stamp (td_unet::use_clock)
     void drop_graph() { if (graph) { (void)hipGraphExecDestroy(graph); graph = nullptr; } }
@@ -443,6 +486,14 @@ static int ensure_packed_s16(td_unet* u, ConvWeights& cw) {
     return TD_OK;
 }
 
+// a host table as a device buffer of its own (setup time: blocking)
+template <typename T> static int upload_new(Buf& b, const std::vector<T>& v) {
+    b.reset(new DevBuf());
+    HIP_TRY(b->alloc(v.size() * sizeof(T), false));
+    HIP_TRY(hipMemcpy(b->p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return TD_OK;
+}
+
 static int finalize(td_unet* u) {
     for (auto& p : u->params) if (!p.set) return fail(TD_ERR_STATE, "parameter not set: " + p.name);
     auto folded = [&](const std::string& n, float gain) -> const std::vector<float>* {
@@ -453,20 +504,12 @@ static int finalize(td_unet* u) {
     int rc;
     if (u->kind != 0) {   // no embedding: one row of ones serves every block and every image (+ slack for the epilogues' 16-byte row reads)
         std::vector<float> ones((size_t)u->g.max_cout + 256, 1.f);
-        u->d_ones.reset(new DevBuf());
-        HIP_TRY(u->d_ones->alloc(ones.size() * 4, false));
-        HIP_TRY(hipMemcpy(u->d_ones->p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice));
+        if ((rc = upload_new(u->d_ones, ones))) return rc;
     }
     // embedding path (fp32 on device)
     if (u->kind == 0) {
-        auto up = [&](Buf& b, const std::vector<float>& v) -> int {
-            b.reset(new DevBuf());
-            HIP_TRY(b->alloc(v.size() * 4, false));
-            HIP_TRY(hipMemcpy(b->p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-            return TD_OK;
-        };
-        if ((rc = up(u->d_freqs, P(u, "noise_fourier.freqs").data))) return rc;
-        if ((rc = up(u->d_wnoise, *folded("noise_linear.weight", 1.f)))) return rc;
+        if ((rc = upload_new(u->d_freqs, P(u, "noise_fourier.freqs").data))) return rc;
+        if ((rc = upload_new(u->d_wnoise, *folded("noise_linear.weight", 1.f)))) return rc;
         {
             std::vector<float> wc, fr;
             EmbDesc& d = u->embd;
@@ -492,7 +535,7 @@ static int finalize(td_unet* u) {
             u->cond_row_len = d.row_len;
             if (wc.empty()) wc.push_back(0.f);
             if (fr.empty()) fr.push_back(0.f);
-            if ((rc = up(u->d_wcond, wc)) || (rc = up(u->d_fourier, fr))) return rc;
+            if ((rc = upload_new(u->d_wcond, wc)) || (rc = upload_new(u->d_fourier, fr))) return rc;
         }
         std::vector<float> wall;
         std::vector<int> woff, coff, cout;
@@ -505,14 +548,8 @@ static int finalize(td_unet* u) {
         for (auto& b : u->g.enc) add(b);
         for (auto& b : u->g.dec) add(b);
         u->n_blocks = (int)woff.size();
-        if ((rc = up(u->d_wemb, wall))) return rc;
-        auto upi = [&](Buf& b, const std::vector<int>& v) -> int {
-            b.reset(new DevBuf());
-            HIP_TRY(b->alloc(v.size() * 4, false));
-            HIP_TRY(hipMemcpy(b->p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-            return TD_OK;
-        };
-        if ((rc = upi(u->d_blk_woff, woff)) || (rc = upi(u->d_blk_coff, coff)) || (rc = upi(u->d_blk_cout, cout))) return rc;
+        if ((rc = upload_new(u->d_wemb, wall))) return rc;
+        if ((rc = upload_new(u->d_blk_woff, woff)) || (rc = upload_new(u->d_blk_coff, coff)) || (rc = upload_new(u->d_blk_cout, cout))) return rc;
     }
     // conv weights per fused op: the weight side of the graph's K-segments
     u->convw.clear();
@@ -792,7 +829,7 @@ static int build_plan(td_unet* u, int N, int H, int W, Plan** out, int lane = 0)
 }
 
 // per-(step,tile) embeddings and per-block modulation vectors for all steps at once (t depends on the step only)
-static int compute_cvecs(td_unet* u, Plan& pl, const std::vector<float>& t_steps, const float* d_cond) {
+static int compute_cvecs(td_unet* u, Plan& pl, const std::vector<float>& t_steps, const float* d_cond, Call& c) {
     hipStream_t st = u->eng->stream;
     const int rows = (int)t_steps.size() * pl.N;
     if (!pl.emb || pl.cvec_rows < rows) {
@@ -807,7 +844,7 @@ static int compute_cvecs(td_unet* u, Plan& pl, const std::vector<float>& t_steps
     }
     // `t_steps` lives on the caller's stack: with option "async" the call may return before the stream gets here, so the (80-byte) upload goes
     // through the engine's pinned ring
-    { int rc_ = upload(u->eng, pl.tsteps->p, t_steps.data(), t_steps.size() * 4); if (rc_) return rc_; }
+    { int rc_ = c.up(pl.tsteps->p, t_steps.data(), t_steps.size() * 4); if (rc_) return rc_; }
     const int half = u->g.noise_dims / 2;
     hipLaunchKernelGGL(emb_kernel, dim3(rows, (u->g.emb_ch + 63) / 64), dim3(256), (size_t)(2 * half + u->embd.feat_total) * 4, st, (const float*)pl.tsteps->p, d_cond, pl.N,
                        (const float*)u->d_freqs->p, half, (const float*)u->d_wnoise->p, (const float*)u->d_wcond->p, (const float*)u->d_fourier->p,
@@ -846,35 +883,72 @@ static hipError_t launch_selected(const ConvParams& p, const ConvSel& s, int dt,
     return hipErrorInvalidValue;
 }
 
+// Option "profile": a HIP event pair around each launch of one call (eager mode).  The destructor waits for the stream once -- a profiled call is
+// not enqueue-only -- and accumulates per label (td_engine_profile_dump) and into the conv / other / LDS-DMA-family totals of the engine.
+struct ProfScope {
+    td_engine* const e;
+    const hipStream_t st;
+    const bool on;
+    struct Rec { hipEvent_t a, b; std::string label; bool conv; double flop; };
+    std::vector<Rec> recs;
+    hipEvent_t open = nullptr;
+    explicit ProfScope(td_engine* e_) : e(e_), st(e_->stream), on(e_->option("profile", 0) != 0) {}
+    void begin() {
+        if (!on || hipEventCreate(&open) != hipSuccess) { open = nullptr; return; }
+        (void)hipEventRecord(open, st);
+    }
+    // `conv`: counted with the conv launches, else with the others; `flop`: the launch's roofline FLOP (0: not part of the LDS-DMA family's total)
+    void end(const std::string& label, bool conv = false, double flop = 0.0) {
+        hipEvent_t b;
+        if (!open || hipEventCreate(&b) != hipSuccess) return;
+        (void)hipEventRecord(b, st);
+        recs.push_back({open, b, label, conv, flop});
+        open = nullptr;
+    }
+    ~ProfScope() {
+        if (open) (void)hipEventDestroy(open);
+        if (recs.empty()) return;
+        (void)hipStreamSynchronize(st);
+        for (const Rec& r : recs) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, r.a, r.b);
+            auto& po = e->prof_ops[r.label]; po.first += ms; po.second++;
+            if (r.flop > 0) { e->prof_glds_ms += ms; e->prof_glds_flop += r.flop; e->prof_glds_launches++; }
+            if (r.conv) { e->prof_conv_ms += ms; e->prof_conv_launches++; } else { e->prof_other_ms += ms; e->prof_other_launches++; }
+            (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b);
+        }
+    }
+};
+
+// profile label of one conv launch: the op's label, its geometry, the selector's tag (x16: conv_glds_wide16.hip; the flavour tag stays f2w) and the
+// algorithmic work of the launch
+static std::string conv_prof_label(const td_unet* u, const Op& op, const ConvParams& p) {
+    // GFLOP: REAL input channels (the 6-channel input conv is 5.4 GFLOP at batch 64, not the 58 its K padding to 64 would give)
+    const double gf = op.k_alg * 2.0 * p.N * p.H * p.W * p.Cout * 1e-9;
+    // HBM megabytes: every source tensor once (at ITS resolution), the residual once, the outputs once, the weights once
+    double mb = 0.0;
+    const double es = (double)u->esize();
+    for (int si = 0; si < p.nseg; ++si) mb += (double)p.N * p.seg[si].Hs * p.seg[si].Ws * p.seg[si].C * es + (double)p.seg[si].C / 64.0 * p.seg[si].taps * p.CoutPad * 128.0 * (es / 2.0);
+    if (p.res) mb += (double)p.N * p.res_Hs * p.res_Ws * p.Cout * es;
+    const double o1 = (double)p.N * p.H * p.W * p.Cout * (p.out_f32 ? 4.0 : es);
+    const double mbs = (mb + o1) * 1e-6;   // strict: without the optional pre-activated second output (an optimisation, not part of the layer's definition)
+    mb += o1 * (p.out2 ? 2.0 : 1.0);
+    mb *= 1e-6;
+    char head[48], nums[112];
+    snprintf(head, sizeof head, " [%dx%d k%d ", p.H, p.W, p.kgroups);
+    snprintf(nums, sizeof nums, " wg%d ks%d gf%.2f mb%.2f mbs%.2f", p.n_ntiles * p.tiles_x * p.tiles_y * p.img_groups, p.ksplit, gf, mb, mbs);
+    return op.label + head + conv_sel_tag(op.sel, nums) + "]";
+}
+
 // runs the conv stack: xin -> F, using modulation vectors of `step`
 // `fuse` (EDM sampler): the output conv runs the DPM-Solver++ update of this step in its epilogue (EPI_DPM_STEP) instead of writing F
 static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = nullptr) {
     hipStream_t st = u->eng->stream;
     const float* cbase = u->kind != 0 ? (const float*)u->d_ones->p : (const float*)pl.cvec->p + (size_t)step * pl.N * u->g.c_total;
-    const bool prof = u->eng->option("profile", 0) != 0;
-    std::vector<hipEvent_t> evs;
-    std::vector<int> ev_kind;
-    std::vector<std::string> ev_label;
-    std::vector<double> ev_flop;
-    auto mark = [&]() { if (prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, st); evs.push_back(e); } };
-    struct Fin {
-        td_unet* u; std::vector<hipEvent_t>& evs; std::vector<int>& kind; std::vector<std::string>& labels; std::vector<double>& flop; hipStream_t st;
-        ~Fin() {
-            if (evs.empty()) return;
-            (void)hipStreamSynchronize(st);
-            for (size_t i = 0; i + 1 < evs.size(); i += 2) {
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
-                auto& po = u->eng->prof_ops[labels[i / 2]]; po.first += ms; po.second++;
-                if (flop[i / 2] > 0) { u->eng->prof_glds_ms += ms; u->eng->prof_glds_flop += flop[i / 2]; u->eng->prof_glds_launches++; }
-                if (kind[i / 2] == 0) { u->eng->prof_conv_ms += ms; u->eng->prof_conv_launches++; } else { u->eng->prof_other_ms += ms; u->eng->prof_other_launches++; }
-            }
-            for (auto e : evs) (void)hipEventDestroy(e);
-        }
-    } fin{u, evs, ev_kind, ev_label, ev_flop, st};
+    ProfScope prof(u->eng);
     for (auto& op : pl.ops) {
         if (op.kind == Op::ATTN) {
-            mark();
+            prof.begin();
             if (op.attn_ws) {   // bf16: pack (de-interleave + unit-RMS norm) -> MFMA flash kernel; unet_block.py:102-108
                 const int Hh = op.C / 64, L = op.tokens;
                 size_t qn, kn, vn;
@@ -889,7 +963,7 @@ static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = null
             TD_DISPATCH_T(u, hipLaunchKernelGGL(ae_attn_wave_kernel<T_>, dim3(pl.N, op.C / 64, (op.tokens + 3) / 4), dim3(256), 0, st, (const T_*)op.qkv, (T_*)op.att, op.tokens, op.C));
             else
             TD_DISPATCH_T(u, hipLaunchKernelGGL(attn_kernel<T_>, dim3(pl.N, op.C / 64), dim3(256), 0, st, (const T_*)op.qkv, (T_*)op.att, op.tokens, op.C));
-            mark(); if (prof) { ev_kind.push_back(1); ev_label.push_back(op.label); ev_flop.push_back(0.0); }
+            prof.end(op.label);
             HIP_TRY(hipGetLastError());
             continue;
         }
@@ -898,24 +972,27 @@ static int run_unet(td_unet* u, Plan& pl, int step, const SchedCoef* fuse = null
         if (fuse && &op == &pl.ops.back()) {   // the output conv (EPI_PLAIN, fp32 F): results go straight into the solver state
             p.epi = EPI_DPM_STEP; p.dpm_x = (float*)pl.x->p; p.dpm_m1 = (float*)pl.m1->p; p.dpm_m2 = u->eng->option("solver_order", 2) == 3 ? (float*)pl.m2->p : nullptr; p.dpm_xin = pl.xin; p.dpm_xin_cstride = u->chunk; p.dpm_k = *fuse;
         }
-        mark();
+        prof.begin();
         hipError_t e = launch_selected(p, op.sel, u->dt, st);
-        mark(); if (prof) { ev_kind.push_back(0); char head[48], nums[112]; double gf_ = op.k_alg * 2.0 * p.N * p.H * p.W * p.Cout * 1e-9;  /* algorithmic GFLOP of this launch: REAL input channels (the 6-channel input conv is 5.4 GFLOP at batch 64, not the 58 its K padding to 64 would give) */
-            /* algorithmic HBM megabytes of this launch: every source tensor once (at ITS resolution), the residual once, the outputs once, the weights once */
-            double mb_ = 0.0; const double es_ = (double)u->esize();
-            for (int si_ = 0; si_ < p.nseg; ++si_) mb_ += (double)p.N * p.seg[si_].Hs * p.seg[si_].Ws * p.seg[si_].C * es_ + (double)p.seg[si_].C / 64.0 * p.seg[si_].taps * p.CoutPad * 128.0 * (es_ / 2.0);
-            if (p.res) mb_ += (double)p.N * p.res_Hs * p.res_Ws * p.Cout * es_;
-            const double o1_ = (double)p.N * p.H * p.W * p.Cout * (p.out_f32 ? 4.0 : es_);
-            const double mbs_ = (mb_ + o1_) * 1e-6;   /* strict: without the optional pre-activated second output (an optimisation, not part of the layer's definition) */
-            mb_ += o1_ * (p.out2 ? 2.0 : 1.0);
-            mb_ *= 1e-6;
-            snprintf(head, sizeof head, " [%dx%d k%d ", p.H, p.W, p.kgroups);
-            snprintf(nums, sizeof nums, " wg%d ks%d gf%.2f mb%.2f mbs%.2f", p.n_ntiles * p.tiles_x * p.tiles_y * p.img_groups, p.ksplit, gf_, mb_, mbs_);
-            ev_label.push_back(op.label + head + conv_sel_tag(op.sel, nums) + "]");   /* x16: conv_glds_wide16.hip; the flavour tag stays f2w */
-            ev_flop.push_back(op.sel.glds_family() ? 2.0 * p.N * p.H * p.W * (double)p.Cout * op.k_alg : 0.0); }   // the LDS-DMA family alone (bench.py's roofline kernel); small-batch launches are told apart by their f4 label
+        // (roofline FLOP for the LDS-DMA family alone: bench.py's roofline kernel; small-batch launches are told apart by their f4 label)
+        if (prof.on) prof.end(conv_prof_label(u, op, p), true, op.sel.glds_family() ? 2.0 * p.N * p.H * p.W * (double)p.Cout * op.k_alg : 0.0);
         if (e != hipSuccess) return fail(TD_ERR_HIP, "conv launch " + op.label + ": " + hipGetErrorString(e));
     }
     return TD_OK;
+}
+
+// debug read-back: NHWC with channel stride `cs`, fp32 (`f32`) or the model's 16-bit storage type, -> planar fp32 [n][C][HW] of its first C channels
+static void widen_nhwc(const td_unet* u, bool f32, const uint8_t* raw, int n, int C, size_t HW, int cs, float* out) {
+    for (int i = 0; i < n; ++i)
+        for (int c = 0; c < C; ++c)
+            for (size_t p = 0; p < HW; ++p) {
+                const size_t src = ((size_t)i * HW + p) * cs + c;
+                float v;
+                if (f32) v = ((const float*)raw)[src];
+                else if (u->dt == TD_DTYPE_F16) { _Float16 h; memcpy(&h, (const uint16_t*)raw + src, 2); v = (float)h; }
+                else { uint32_t b = (uint32_t)((const uint16_t*)raw)[src] << 16; memcpy(&v, &b, 4); }
+                out[((size_t)i * C + c) * HW + p] = v;
+            }
 }
 
 static inline dim3 grid1(size_t n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
@@ -1070,30 +1147,28 @@ int td_unet_finalize(td_unet* u) {
 int td_unet_cond_row_len(td_unet* u) { return u->cond_row_len; }
 
 int td_unet_forward(td_unet* u, int n, int H, int W, const float* x, const float* t_host, const float* cond, float* out) {
-    DevGuard dg_(u->eng->device);
+    Call c(u->eng);
     if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
     Plan* pl;
     int rc = build_plan(u, n, H, W, &pl);
     if (rc) return rc;
-    td_engine* e = u->eng;
-    hipStream_t st = e->stream;
+    hipStream_t st = c.e->stream;
     const int C = u->cfg.in_channels, Co = u->cfg.out_channels, HW = H * W;
-    std::vector<Buf> hold;
-    const void *dx, *dcond = nullptr;
-    if ((rc = to_device(e, x, (size_t)n * C * HW * 4, hold, &dx))) return rc;
-    if (u->cond_row_len > 0 && (rc = to_device(e, cond, (size_t)n * u->cond_row_len * 4, hold, &dcond))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, out, (size_t)n * Co * HW * 4, hold, &os))) return rc;
+    const float *dx, *dcond = nullptr;
+    float* dout;
+    if ((rc = c.in(x, (size_t)n * C * HW * 4, &dx))) return rc;
+    if (u->cond_row_len > 0 && (rc = c.in(cond, (size_t)n * u->cond_row_len * 4, &dcond))) return rc;
+    if ((rc = c.out(out, (size_t)n * Co * HW * 4, &dout))) return rc;
     // per-sample t: treat every sample as its own "step" row set (rows = n steps x n tiles would be wasteful): run per distinct t
     // general case: one embedding row per sample -> emulate with steps=n, tiles=n and pick row i*n+i.  Keep it simple: loop unique t values.
     std::vector<float> ts(t_host, t_host + n);
     bool uniform = true;
     for (int i = 1; i < n; ++i) uniform = uniform && ts[i] == ts[0];
     if (uniform) {
-        if ((rc = compute_cvecs(u, *pl, std::vector<float>(1, ts[0]), (const float*)dcond))) return rc;
+        if ((rc = compute_cvecs(u, *pl, std::vector<float>(1, ts[0]), dcond, c))) return rc;
     } else {
         // rows = n "steps" x n tiles; sample i uses row i*n + i.  Build a compact [n][c_total] table by copying those rows to step 0's slot.
-        if ((rc = compute_cvecs(u, *pl, ts, (const float*)dcond))) return rc;
+        if ((rc = compute_cvecs(u, *pl, ts, dcond, c))) return rc;
         for (int i = 1; i < n; ++i) {
             HIP_TRY(hipMemcpyAsync((float*)pl->cvec->p + (size_t)i * u->g.c_total, (float*)pl->cvec->p + ((size_t)i * n + i) * u->g.c_total, (size_t)u->g.c_total * 4,
                                    hipMemcpyDeviceToDevice, st));
@@ -1101,13 +1176,11 @@ int td_unet_forward(td_unet* u, int n, int H, int W, const float* x, const float
                                    hipMemcpyDeviceToDevice, st));
         }
     }
-    TD_DISPATCH_T(u, hipLaunchKernelGGL(prep_input_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)dx, (T_*)pl->xin, n, C, HW, u->chunk, 1.f, C));
+    TD_DISPATCH_T(u, hipLaunchKernelGGL(prep_input_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, dx, (T_*)pl->xin, n, C, HW, u->chunk, 1.f, C));
     if ((rc = run_unet(u, *pl, 0))) return rc;
-    hipLaunchKernelGGL(unpack_output_kernel, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)pl->F, (float*)os.dev, n, Co, HW, 8, 1.f);
+    hipLaunchKernelGGL(unpack_output_kernel, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)pl->F, dout, n, Co, HW, 8, 1.f);
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, os))) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    return TD_OK;
+    return c.finish(true);
 }
 
 int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, float* out_host, int64_t capacity, int32_t dims[4]) {
@@ -1154,16 +1227,7 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
         HIP_TRY(hipStreamSynchronize(u->eng->stream));
         std::vector<uint8_t> raw(elems * (u->bf16 ? 2 : 4));
         HIP_TRY(hipMemcpy(raw.data(), pl->xin, raw.size(), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i)
-            for (int c = 0; c < cs; ++c)
-                for (size_t p = 0; p < HW; ++p) {
-                    const size_t src = ((size_t)i * HW + p) * cs + c;
-                    float v;
-                    if (!u->bf16) v = ((const float*)raw.data())[src];
-                    else if (u->dt == TD_DTYPE_F16) { _Float16 h; memcpy(&h, (const uint16_t*)raw.data() + src, 2); v = (float)h; }
-                    else { uint32_t b = (uint32_t)((const uint16_t*)raw.data())[src] << 16; memcpy(&v, &b, 4); }
-                    out_host[((size_t)i * cs + c) * HW + p] = v;
-                }
+        widen_nhwc(u, !u->bf16, raw.data(), n, cs, HW, cs, out_host);
         return TD_OK;
     }
     if (!strncmp(label, "sumsq:", 6)) {
@@ -1192,16 +1256,7 @@ int td_unet_read_activation(td_unet* u, int n, int H, int W, const char* label, 
         const bool f32out = (!is_attn && op.p.out_f32) || !u->bf16;
         std::vector<uint8_t> raw(elems * (f32out ? 4 : 2));
         HIP_TRY(hipMemcpy(raw.data(), is_attn ? op.att : op.p.out, raw.size(), hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i)
-            for (int c = 0; c < C; ++c)
-                for (int p = 0; p < h * w; ++p) {
-                    size_t src = ((size_t)i * h * w + p) * cs + c;
-                    float v;
-                    if (f32out) v = ((const float*)raw.data())[src];
-                    else if (u->dt == TD_DTYPE_F16) { _Float16 h; memcpy(&h, (const uint16_t*)raw.data() + src, 2); v = (float)h; }
-                    else { uint32_t b = (uint32_t)((const uint16_t*)raw.data())[src] << 16; memcpy(&v, &b, 4); }
-                    out_host[((size_t)i * C + c) * h * w + p] = v;
-                }
+        widen_nhwc(u, f32out, raw.data(), n, C, (size_t)h * w, cs, out_host);
         return TD_OK;
     }
     return fail(TD_ERR_ARG, std::string("no conv or attention op labelled ") + label);
@@ -1262,25 +1317,27 @@ int td_dpm_coefs(const float* sigmas_host, int n_steps, float sigma_data, int so
 }
 
 // writes the conditioning-image channels [Cs, Cs+cimg) of the NHWC model input (constant over the solver steps)
-static int stage_cond_img(td_unet* u, Plan& pl, int n, int HW, const float* cond_img, int cimg, int Cs, std::vector<Buf>& hold) {
-    if (cimg == 0) return TD_OK;
+static int stage_cond_img(td_unet* u, Plan& pl, int n, int HW, const float* cond_img, int cimg, int Cs, Call& c) {
+    if (cimg == 0) { c.direct(cond_img); return TD_OK; }   // (not read, but a host pointer here has always made the call end synchronously)
     if (!cond_img) return fail(TD_ERR_ARG, "cond_img is null");
-    const void* dimg;
-    int rc = to_device(u->eng, cond_img, (size_t)n * cimg * HW * 4, hold, &dimg);
+    const float* dimg;
+    int rc = c.in(cond_img, (size_t)n * cimg * HW * 4, &dimg);
     if (rc) return rc;
     hipStream_t st = u->eng->stream;
-    TD_DISPATCH_T(u, hipLaunchKernelGGL(write_cond_img_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)dimg, (T_*)pl.xin, n, cimg, HW, u->chunk, Cs));
+    TD_DISPATCH_T(u, hipLaunchKernelGGL(write_cond_img_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, dimg, (T_*)pl.xin, n, cimg, HW, u->chunk, Cs));
     HIP_TRY(hipGetLastError());
     return TD_OK;
 }
 
-// score scaling of a sampler call (td_sample_edm_ext): alpha == 1 is off and reads nothing else
-struct ScoreArgs { float alpha = 1.f; const float* cs_host = nullptr; };
-
-// One lane of the batched EDM sampler: everything is enqueued on e->stream (the caller swaps the engine's streams for the second lane) and
-// NOT waited for; temporaries that must outlive the queue go to `hold`.
-static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
-                           const float* cond, const float* cond_img, int cimg, float* x, int lane, std::vector<Buf>& hold, const ScoreArgs& sa) {
+// One lane of the batched EDM sampler, on the arguments of td_sample_edm_ext (guide == NULL: guidance_scale is 1; score_scaling == 1 is off and reads
+// nothing else): everything is enqueued on e->stream (the caller swaps the engine's streams for the second lane) and NOT waited for; temporaries
+// that must outlive the queue go to the call scope.
+static int sample_edm_lane(td_unet* u, const td_edm_ext& a, int lane, Call& c) {
+    td_unet* const guide = a.guide;
+    const int n = a.n, H = a.H, W = a.W, n_steps = a.n_steps, cimg = a.cimg_channels;
+    const float gscale = a.guidance_scale, sigma_data = a.sigma_data, alpha = a.score_scaling;
+    const float *sigmas_host = a.sigmas_host, *cond = a.cond, *cond_img = a.cond_img;
+    float* const x = a.x;
     if (guide) {
         if (!guide->finalized) return fail(TD_ERR_STATE, "finalize the guide model first");
         if (guide->eng != u->eng || guide->dt != u->dt) return fail(TD_ERR_ARG, "guide model must live on the same engine and use the same dtype");
@@ -1289,10 +1346,9 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
     }
     if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
     if (n_steps < 1) return fail(TD_ERR_ARG, "n_steps");
-    const float alpha = sa.alpha;
-    if (alpha != 1.f && !sa.cs_host) return fail(TD_ERR_ARG, "score_scaling != 1 needs score_cs_host (n_steps pairs cos t_i, sin t_i)");
+    if (alpha != 1.f && !a.score_cs_host) return fail(TD_ERR_ARG, "score_scaling != 1 needs score_cs_host (n_steps pairs cos t_i, sin t_i)");
     if (!std::isfinite(alpha)) return fail(TD_ERR_ARG, "score_scaling must be finite");
-    const std::vector<float> cs = alpha != 1.f ? std::vector<float>(sa.cs_host, sa.cs_host + 2 * (size_t)n_steps) : std::vector<float>();
+    const std::vector<float> cs = alpha != 1.f ? std::vector<float>(a.score_cs_host, a.score_cs_host + 2 * (size_t)n_steps) : std::vector<float>();
     Plan* pl;
     int rc = build_plan(u, n, H, W, &pl, lane);
     if (rc) return rc;
@@ -1301,26 +1357,27 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
     const int Cin = u->cfg.in_channels, C = u->cfg.out_channels, HW = H * W;
     if (C + cimg != Cin) return fail(TD_ERR_ARG, "in_channels must equal out_channels + conditioning-image channels");
     const size_t xbytes = (size_t)n * C * HW * 4;
-    const bool x_dev = is_device_ptr(x);
+    const bool x_dev = c.direct(x), cond_dev = c.direct(cond);
     HIP_TRY(hipMemcpyAsync(pl->x->p, x, xbytes, x_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     if (u->cond_row_len > 0) {
         const size_t cb = (size_t)n * u->cond_row_len * 4;
-        HIP_TRY(hipMemcpyAsync(pl->cond->p, cond, cb, is_device_ptr(cond) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pl->cond->p, cond, cb, cond && cond_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     }
-    if ((rc = stage_cond_img(u, *pl, n, HW, cond_img, cimg, C, hold))) return rc;
+    if ((rc = stage_cond_img(u, *pl, n, HW, cond_img, cimg, C, c))) return rc;
     std::vector<float> ts(n_steps);
     for (int i = 0; i < n_steps; ++i) ts[i] = atanf(sigmas_host[i] / sigma_data);  // trigflow_precondition_noise (dpmsolver.py:240-242)
-    if ((rc = compute_cvecs(u, *pl, ts, (const float*)pl->cond->p))) return rc;
+    if ((rc = compute_cvecs(u, *pl, ts, (const float*)pl->cond->p, c))) return rc;
     Plan* gpl = nullptr;
     if (guide) {
         if ((rc = build_plan(guide, n, H, W, &gpl, lane))) return rc;
-        if ((rc = stage_cond_img(guide, *gpl, n, HW, cond_img, cimg, C, hold))) return rc;
-        if ((rc = compute_cvecs(guide, *gpl, ts, (const float*)pl->cond->p))) return rc;
+        if ((rc = stage_cond_img(guide, *gpl, n, HW, cond_img, cimg, C, c))) return rc;
+        if ((rc = compute_cvecs(guide, *gpl, ts, (const float*)pl->cond->p, c))) return rc;
     }
     std::vector<SchedCoef> ks;
     const int solver_order = (int)e->option("solver_order", 2);
     if (solver_order < 1 || solver_order > 3) return fail(TD_ERR_ARG, "solver_order must be 1, 2 or 3");
     const bool lof = e->option("lower_order_final", 1) != 0;
+    const int fuse_opt = (int)e->option("fuse_solver", 1);
     dpm_coefs(sigmas_host, n_steps, sigma_data, solver_order, lof, ks);
     const float c_in0 = 1.f / sqrtf(sigmas_host[0] * sigmas_host[0] + sigma_data * sigma_data);
     // option "sampler_stop_after" = k >= 0 (test read-back): the table is that of the n_steps-step run, only its first k steps are enqueued, and the
@@ -1342,7 +1399,7 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
         // north_star: "the per-tile EDM scheduler step fused into the epilogue".  Without a guide model the solver update of step i runs in the
         // epilogue of the U-Net's output conv (option "fuse_solver", default on; bit-identical to the separate kernel: same arithmetic on the same
         // fp32 F); with autoguidance the update needs BOTH models' outputs and stays a kernel of its own.
-        const bool fuse = !gpl && alpha == 1.f && e->option("fuse_solver", 1) != 0 && pl->ops.back().kind == Op::CONV && pl->ops.back().p.epi == EPI_PLAIN && pl->ops.back().p.out_f32;
+        const bool fuse = !gpl && alpha == 1.f && fuse_opt != 0 && pl->ops.back().kind == Op::CONV && pl->ops.back().p.epi == EPI_PLAIN && pl->ops.back().p.out_f32;
         for (int i = 0; i < n_run; ++i) {
             int r = run_unet(u, *pl, i, fuse ? &ks[i] : nullptr);
             if (r) return r;
@@ -1361,12 +1418,13 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
 
     const bool use_graph = e->option("graph", 1) != 0 && e->option("profile", 0) == 0;
     if (use_graph) {
-        std::vector<float> sg(sigmas_host, sigmas_host + n_steps + 1);
+        GraphKey key;
+        key.sigmas.assign(sigmas_host, sigmas_host + n_steps + 1); key.sigma_data = sigma_data; key.solver_order = solver_order;
+        key.lof = (int)lof; key.fuse = fuse_opt; key.stop = stop_after;
         // the guide's plan can be evicted / its buffers re-allocated independently of this plan: key the graph on them too
-        const void* gkey = gpl ? (const void*)gpl->cvec->p : nullptr;
-        if (!pl->graph || pl->graph_sigmas != sg || pl->graph_sigma_data != sigma_data || pl->graph_solver_order != solver_order || pl->graph_lof != (int)lof ||
-            pl->graph_guide != (const void*)gpl || pl->graph_guide_cvec != gkey || pl->graph_gscale != gscale || pl->graph_fuse != (int)e->option("fuse_solver", 1) ||
-            pl->graph_stop != stop_after || pl->graph_alpha != alpha || pl->graph_cs != cs) {
+        key.guide = gpl; key.guide_cvec = gpl ? (const void*)gpl->cvec->p : nullptr; key.gscale = gscale;
+        key.alpha = alpha; key.cs = cs;
+        if (!pl->graph || !(pl->graph_key == key)) {
             pl->drop_graph();
             hipGraph_t g = nullptr;
             HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -1377,10 +1435,7 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
             hipError_t ie = hipGraphInstantiate(&pl->graph, g, nullptr, nullptr, 0);
             (void)hipGraphDestroy(g);
             if (ie != hipSuccess) { pl->graph = nullptr; return fail(TD_ERR_HIP, std::string("graph instantiate: ") + hipGetErrorString(ie)); }
-            pl->graph_sigmas = sg; pl->graph_sigma_data = sigma_data; pl->graph_solver_order = solver_order; pl->graph_lof = (int)lof; pl->graph_fuse = (int)e->option("fuse_solver", 1);
-            pl->graph_stop = stop_after;
-            pl->graph_guide = gpl; pl->graph_guide_cvec = gkey; pl->graph_gscale = gscale;
-            pl->graph_alpha = alpha; pl->graph_cs = cs;
+            pl->graph_key = std::move(key);
         }
         HIP_TRY(hipGraphLaunch(pl->graph, st));
     } else if ((rc = enqueue())) return rc;
@@ -1399,24 +1454,29 @@ static int sample_edm_lane(td_unet* u, td_unet* guide, float gscale, int n, int 
 // td_engine_set_stream -- are complete before lane two reads them) and the first lane's stream waits for the second at the end, so that the call ends
 // like a single-lane one: results ordered on the engine's stream, enqueue-only under option "async".
 // The sampler's body, enqueue-only: one lane or two on the engine's streams, ending ordered on e->stream.  On failure both streams are drained.
-static int sample_edm_enqueue(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
-                              const float* cond, const float* cond_img, int cimg, float* x, std::vector<Buf>& hold, const ScoreArgs& sa = ScoreArgs()) {
+static int sample_edm_enqueue(td_unet* u, const td_edm_ext& a, Call& c) {
     td_engine* e = u->eng;
+    const int n = a.n;
     const bool dual = e->stream2 && e->option("dual_stream", 1) != 0 && n >= std::max<int64_t>(2, e->option("dual_stream_min_batch", 32));
     const bool concurrent = e->option("profile", 0) == 0;  // profile mode times every launch with events on ONE stream: the lanes run one after the other
     if (!dual) {
-        int rc = sample_edm_lane(u, guide, gscale, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, 0, hold, sa);
+        int rc = sample_edm_lane(u, a, 0, c);
         if (rc) (void)hipStreamSynchronize(e->stream);
         return rc;
     }
-    const int nA = n / 2, nB = n - nA, C = u->cfg.out_channels;
-    const size_t HW = (size_t)H * W;
+    // the second lane: the same call on the rest of the batch
+    const int nA = n / 2, C = u->cfg.out_channels;
+    const size_t HW = (size_t)a.H * a.W;
+    td_edm_ext la = a, lb = a;
+    la.n = nA; lb.n = n - nA;
+    lb.cond = a.cond ? a.cond + (size_t)nA * u->cond_row_len : nullptr;
+    lb.cond_img = a.cond_img ? a.cond_img + (size_t)nA * a.cimg_channels * HW : nullptr;
+    lb.x = a.x + (size_t)nA * C * HW;
     if (concurrent) { HIP_TRY(hipEventRecord(e->ev_fork, e->stream)); HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_fork, 0)); }
-    int rc = sample_edm_lane(u, guide, gscale, nA, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, 0, hold, sa);
+    int rc = sample_edm_lane(u, la, 0, c);
     if (!rc) {
         if (concurrent) std::swap(e->stream, e->stream2);
-        rc = sample_edm_lane(u, guide, gscale, nB, H, W, n_steps, sigmas_host, sigma_data, cond ? cond + (size_t)nA * u->cond_row_len : nullptr,
-                             cond_img ? cond_img + (size_t)nA * cimg * HW : nullptr, cimg, x + (size_t)nA * C * HW, 1, hold, sa);
+        rc = sample_edm_lane(u, lb, 1, c);
         if (concurrent) std::swap(e->stream, e->stream2);
     }
     if (rc) { (void)hipStreamSynchronize(e->stream); (void)hipStreamSynchronize(e->stream2); return rc; }
@@ -1424,73 +1484,78 @@ static int sample_edm_enqueue(td_unet* u, td_unet* guide, float gscale, int n, i
     return TD_OK;
 }
 
-static int sample_edm_impl(td_unet* u, td_unet* guide, float gscale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
-                           const float* cond, const float* cond_img, int cimg, float* x, const ScoreArgs& sa = ScoreArgs()) {
-    td_engine* e = u->eng;
-    DevGuard dg_(e->device);
-    std::vector<Buf> hold;
-    const bool all_dev = is_device_ptr(x) && (!cond || is_device_ptr(cond)) && (!cond_img || is_device_ptr(cond_img));
-    int rc = sample_edm_enqueue(u, guide, gscale, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x, hold, sa);
-    if (rc) return rc;
-    // default: results complete on return (the caller's framework uses other streams); option "async": left enqueued on e->stream
-    return end_call(e, hold, all_dev);
+// default: results complete on return (the caller's framework uses other streams); option "async": left enqueued on e->stream
+static int sample_edm_impl(td_unet* u, const td_edm_ext& a) {
+    Call c(u->eng);
+    int rc = sample_edm_enqueue(u, a, c);
+    return rc ? rc : c.finish();
+}
+
+// the plain sampler's arguments as the struct: no guide, no score scaling
+static td_edm_ext edm_args(int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data, const float* cond, const float* cond_img, int cimg, float* x) {
+    td_edm_ext a;
+    memset(&a, 0, sizeof a);
+    a.n = n; a.H = H; a.W = W; a.n_steps = n_steps; a.sigmas_host = sigmas_host; a.sigma_data = sigma_data;
+    a.cond = cond; a.cond_img = cond_img; a.cimg_channels = cimg; a.x = x;
+    a.guidance_scale = 1.f; a.score_scaling = 1.f;
+    return a;
 }
 
 int td_sample_edm_img(td_unet* u, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data, const float* cond,
                       const float* cond_img, int cimg, float* x) {
-    return sample_edm_impl(u, nullptr, 1.f, n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x);
+    return sample_edm_impl(u, edm_args(n, H, W, n_steps, sigmas_host, sigma_data, cond, cond_img, cimg, x));
 }
 int td_sample_edm(td_unet* u, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data, const float* cond, float* x) {
-    return sample_edm_impl(u, nullptr, 1.f, n, H, W, n_steps, sigmas_host, sigma_data, cond, nullptr, 0, x);
+    return sample_edm_impl(u, edm_args(n, H, W, n_steps, sigmas_host, sigma_data, cond, nullptr, 0, x));
 }
 int td_sample_edm_guided(td_unet* u, td_unet* guide, float guidance_scale, int n, int H, int W, int n_steps, const float* sigmas_host, float sigma_data,
                          const float* cond, float* x) {
     if (!guide) return fail(TD_ERR_ARG, "null guide model");
-    return sample_edm_impl(u, guide, guidance_scale, n, H, W, n_steps, sigmas_host, sigma_data, cond, nullptr, 0, x);
+    td_edm_ext a = edm_args(n, H, W, n_steps, sigmas_host, sigma_data, cond, nullptr, 0, x);
+    a.guide = guide; a.guidance_scale = guidance_scale;
+    return sample_edm_impl(u, a);
 }
 
 // Every argument of the EDM sampler in one struct: conditioning-image channels, a guide model and score scaling in any combination.  With no
 // guide (or scale 1), score_scaling == 1 it is the call td_sample_edm_img makes; the guide's plan gets the same cond_img staged as the main one.
-int td_sample_edm_ext(td_unet* u, const td_edm_ext* a) {
-    if (!u || !a) return fail(TD_ERR_ARG, "td_sample_edm_ext: null argument");
-    if (!a->sigmas_host || !a->x) return fail(TD_ERR_ARG, "td_sample_edm_ext: sigmas_host / x is null");
-    if (a->cimg_channels < 0 || (a->cimg_channels > 0 && !a->cond_img)) return fail(TD_ERR_ARG, "td_sample_edm_ext: cond_img is null");
-    ScoreArgs sa;
-    sa.alpha = a->score_scaling; sa.cs_host = a->score_cs_host;
-    return sample_edm_impl(u, a->guide, a->guide ? a->guidance_scale : 1.f, a->n, a->H, a->W, a->n_steps, a->sigmas_host, a->sigma_data, a->cond,
-                           a->cimg_channels > 0 ? a->cond_img : nullptr, a->cimg_channels, a->x, sa);
+int td_sample_edm_ext(td_unet* u, const td_edm_ext* args) {
+    if (!u || !args) return fail(TD_ERR_ARG, "td_sample_edm_ext: null argument");
+    td_edm_ext a = *args;
+    if (!a.sigmas_host || !a.x) return fail(TD_ERR_ARG, "td_sample_edm_ext: sigmas_host / x is null");
+    if (a.cimg_channels < 0 || (a.cimg_channels > 0 && !a.cond_img)) return fail(TD_ERR_ARG, "td_sample_edm_ext: cond_img is null");
+    if (!a.guide) a.guidance_scale = 1.f;
+    if (a.cimg_channels == 0) a.cond_img = nullptr;
+    return sample_edm_impl(u, a);
 }
 
 int td_sample_consistency_img(td_unet* u, int n, int H, int W, float t, float sigma_data, const float* sample, const float* z, const float* cond,
                               const float* cond_img, int cimg, float* out) {
-    DevGuard dg_(u->eng->device);
+    Call c(u->eng);
     if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
     Plan* pl;
     int rc = build_plan(u, n, H, W, &pl);
     if (rc) return rc;
-    td_engine* e = u->eng;
-    hipStream_t st = e->stream;
+    hipStream_t st = c.e->stream;
     const int Cin = u->cfg.in_channels, C = u->cfg.out_channels, HW = H * W;
     if (C + cimg != Cin) return fail(TD_ERR_ARG, "in_channels must equal out_channels + conditioning-image channels");
     const size_t xbytes = (size_t)n * C * HW * 4;
-    std::vector<Buf> hold;
-    const void* dz;
-    if ((rc = to_device(e, z, xbytes, hold, &dz))) return rc;
-    if (sample) HIP_TRY(hipMemcpyAsync(pl->x->p, sample, xbytes, is_device_ptr(sample) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    const float* dz;
+    if ((rc = c.in(z, xbytes, &dz))) return rc;
+    const bool cond_dev = c.direct(cond);
+    if (sample) HIP_TRY(hipMemcpyAsync(pl->x->p, sample, xbytes, c.direct(sample) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     else HIP_TRY(hipMemsetAsync(pl->x->p, 0, xbytes, st));
     if (u->cond_row_len > 0)
-        HIP_TRY(hipMemcpyAsync(pl->cond->p, cond, (size_t)n * u->cond_row_len * 4, is_device_ptr(cond) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    if ((rc = stage_cond_img(u, *pl, n, HW, cond_img, cimg, C, hold))) return rc;
-    if ((rc = compute_cvecs(u, *pl, std::vector<float>(1, t), (const float*)pl->cond->p))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, out, xbytes, hold, &os))) return rc;
+        HIP_TRY(hipMemcpyAsync(pl->cond->p, cond, (size_t)n * u->cond_row_len * 4, cond && cond_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if ((rc = stage_cond_img(u, *pl, n, HW, cond_img, cimg, C, c))) return rc;
+    if ((rc = compute_cvecs(u, *pl, std::vector<float>(1, t), (const float*)pl->cond->p, c))) return rc;
+    float* dout;
+    if ((rc = c.out(out, xbytes, &dout))) return rc;
     const float ct = cosf(t), sn = sinf(t);
-    TD_DISPATCH_T(u, hipLaunchKernelGGL(consistency_pre_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)pl->x->p, (const float*)dz, (float*)pl->xt->p, (T_*)pl->xin, n, C, HW, u->chunk, ct, sn, sigma_data, Cin));
+    TD_DISPATCH_T(u, hipLaunchKernelGGL(consistency_pre_kernel<T_>, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)pl->x->p, dz, (float*)pl->xt->p, (T_*)pl->xin, n, C, HW, u->chunk, ct, sn, sigma_data, Cin));
     if ((rc = run_unet(u, *pl, 0))) return rc;
-    hipLaunchKernelGGL(consistency_post_kernel, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)pl->xt->p, (const float*)pl->F, (float*)os.dev, n, C, HW, 8, ct, sn, sigma_data);
+    hipLaunchKernelGGL(consistency_post_kernel, grid1((size_t)n * HW), dim3(256), 0, st, (const float*)pl->xt->p, (const float*)pl->F, dout, n, C, HW, 8, ct, sn, sigma_data);
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, os))) return rc;
-    return end_call(e, hold, !os.host && is_device_ptr(z) && (!sample || is_device_ptr(sample)) && (!cond || is_device_ptr(cond)) && (!cond_img || is_device_ptr(cond_img)));
+    return c.finish();
 }
 
 int td_sample_consistency(td_unet* u, int n, int H, int W, float t, float sigma_data, const float* sample, const float* z, const float* cond, float* out) {
@@ -1507,33 +1572,32 @@ uint64_t td_tile_seed(uint64_t base_seed, int64_t ty, int64_t tx) {
 }
 
 int td_standard_normal(td_engine* e, uint64_t seed, int64_t n, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (n <= 0) return TD_OK;
-    std::vector<Buf> hold;
-    OutStage os;
+    float* dout;
     int rc;
-    if ((rc = out_device(e, out, (size_t)n * 4, hold, &os))) return rc;
+    if ((rc = c.out(out, (size_t)n * 4, &dout))) return rc;
     Buf sd(new DevBuf());
     HIP_TRY(sd->alloc(8, false));
     HIP_TRY(hipMemcpyAsync(sd->p, &seed, 8, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(noise_tiles_kernel, dim3(1), dim3(256), 0, e->stream, (const uint64_t*)sd->p, (float*)os.dev, n);
+    hipLaunchKernelGGL(noise_tiles_kernel, dim3(1), dim3(256), 0, e->stream, (const uint64_t*)sd->p, dout, n);
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, os))) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return TD_OK;
+    return c.finish(true);
 }
 
 static inline int64_t fdiv(int64_t a, int64_t b) { int64_t q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
 
 // td_noise_patches in two halves: host preparation with its uploads, and the two launches.  NoiseJob owns the host arrays the uploads read
-// (they have to outlive a copy that has not run yet) and the device scratch.
+// (they have to outlive a copy that has not run yet: declared before the Call); the device side lives in the call scope.
 struct NoiseJob {
     std::vector<uint64_t> seeds;
     std::vector<int> index, org;
-    Buf dseeds, dtiles, dindex, dorg;
+    const uint64_t* dseeds = nullptr;
+    float* dtiles = nullptr;
+    const int *dindex = nullptr, *dorg = nullptr;
     int64_t tn = 0;
 };
-static int noise_prepare(td_engine* e, NoiseJob& j, uint64_t base_seed, int n_windows, const int64_t* origins, int h, int w, int channels, int tile_h, int tile_w) {
+static int noise_prepare(Call& c, NoiseJob& j, uint64_t base_seed, int n_windows, const int64_t* origins, int h, int w, int channels, int tile_h, int tile_w) {
     if (h > tile_h || w > tile_w) return fail(TD_ERR_UNSUPPORTED, "window larger than the noise tile");
     // unique noise tiles touched by the windows
     std::map<std::pair<int64_t, int64_t>, int> slot;
@@ -1554,36 +1618,31 @@ static int noise_prepare(td_engine* e, NoiseJob& j, uint64_t base_seed, int n_wi
             }
     }
     j.tn = (int64_t)channels * tile_h * tile_w;
-    j.dseeds.reset(new DevBuf()); j.dtiles.reset(new DevBuf()); j.dindex.reset(new DevBuf()); j.dorg.reset(new DevBuf());
-    HIP_TRY(j.dseeds->scratch(e->scratch, seeds.size() * 8)); HIP_TRY(j.dtiles->scratch(e->scratch, seeds.size() * j.tn * 4));
-    HIP_TRY(j.dindex->scratch(e->scratch, index.size() * 4)); HIP_TRY(j.dorg->scratch(e->scratch, org.size() * 4));
     int rc;
-    if ((rc = upload(e, j.dseeds->p, seeds.data(), seeds.size() * 8)) || (rc = upload(e, j.dindex->p, index.data(), index.size() * 4)) ||
-        (rc = upload(e, j.dorg->p, org.data(), org.size() * 4))) return rc;
+    if ((rc = c.table(seeds.data(), seeds.size() * 8, &j.dseeds)) || (rc = c.scratch(seeds.size() * j.tn * 4, &j.dtiles)) ||
+        (rc = c.table(index.data(), index.size() * 4, &j.dindex)) || (rc = c.table(org.data(), org.size() * 4, &j.dorg))) return rc;
     return TD_OK;
 }
 static int noise_enqueue(td_engine* e, const NoiseJob& j, int n_windows, int h, int w, int channels, int tile_h, int tile_w, float scale, float* out_dev) {
     hipStream_t st = e->stream;
-    hipLaunchKernelGGL(noise_tiles_kernel, dim3((unsigned)j.seeds.size()), dim3(256), 0, st, (const uint64_t*)j.dseeds->p, (float*)j.dtiles->p, j.tn);
-    hipLaunchKernelGGL(noise_gather_kernel, dim3((channels * h * w + 255) / 256, n_windows), dim3(256), 0, st, (const float*)j.dtiles->p, (const int*)j.dindex->p,
-                       (const int*)j.dorg->p, out_dev, channels, h, w, tile_h, tile_w, scale);
+    hipLaunchKernelGGL(noise_tiles_kernel, dim3((unsigned)j.seeds.size()), dim3(256), 0, st, j.dseeds, j.dtiles, j.tn);
+    hipLaunchKernelGGL(noise_gather_kernel, dim3((channels * h * w + 255) / 256, n_windows), dim3(256), 0, st, (const float*)j.dtiles, j.dindex,
+                       j.dorg, out_dev, channels, h, w, tile_h, tile_w, scale);
     HIP_TRY(hipGetLastError());
     return TD_OK;
 }
 
 int td_noise_patches(td_engine* e, uint64_t base_seed, int n_windows, const int64_t* origins, int h, int w, int channels, int tile_h, int tile_w,
                      float scale, float* out) {
-    DevGuard dg_(e->device);
-    if (n_windows <= 0) return TD_OK;
     NoiseJob j;
+    Call c(e);
+    if (n_windows <= 0) return TD_OK;
     int rc;
-    if ((rc = noise_prepare(e, j, base_seed, n_windows, origins, h, w, channels, tile_h, tile_w))) return rc;
-    std::vector<Buf> hold;
-    OutStage os;
-    if ((rc = out_device(e, out, (size_t)n_windows * channels * h * w * 4, hold, &os))) return rc;
-    if ((rc = noise_enqueue(e, j, n_windows, h, w, channels, tile_h, tile_w, scale, (float*)os.dev))) return rc;
-    if ((rc = out_finish(e, os))) return rc;
-    return end_call(e, hold, !os.host);
+    if ((rc = noise_prepare(c, j, base_seed, n_windows, origins, h, w, channels, tile_h, tile_w))) return rc;
+    float* dout;
+    if ((rc = c.out(out, (size_t)n_windows * channels * h * w * 4, &dout))) return rc;
+    if ((rc = noise_enqueue(e, j, n_windows, h, w, channels, tile_h, tile_w, scale, dout))) return rc;
+    return c.finish();
 }
 
 // ---- blend
@@ -1614,9 +1673,10 @@ int td_linear_weight_window(td_engine* e, int size, float* out) {
 struct BlendJob {
     std::vector<int> rowmap, colmap, tile_of;
     std::vector<float> ww;
-    Buf drow, dcol, drs, dcs, dtof, dww;
+    const int32_t *drow = nullptr, *dcol = nullptr, *drs = nullptr, *dcs = nullptr, *dtof = nullptr;
+    const float* dww = nullptr;
 };
-static int blend_prepare(td_engine* e, BlendJob& j, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols, const int32_t* col_starts,
+static int blend_prepare(Call& c, BlendJob& j, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols, const int32_t* col_starts,
                          int n_tiles, const int32_t* wi, const int32_t* wj, const float* window = nullptr) {
     if (C + 1 > 8) return fail(TD_ERR_UNSUPPORTED, "C+1 must be <= 8");
     std::vector<int>& rowmap = j.rowmap; std::vector<int>& colmap = j.colmap; std::vector<int>& tile_of = j.tile_of;
@@ -1645,20 +1705,16 @@ static int blend_prepare(td_engine* e, BlendJob& j, int C, int Hc, int Wc, int s
         j.ww.resize((size_t)size * size);
         HIP_TRY(hipMemcpy(j.ww.data(), window, j.ww.size() * 4, is_device_ptr(window) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
     }
-    auto up = [&](const void* src, size_t bytes, Buf& b) -> int {
-        b.reset(new DevBuf());
-        HIP_TRY(b->scratch(e->scratch, bytes));
-        return upload(e, b->p, src, bytes);
-    };
     int rc;
-    if ((rc = up(rowmap.data(), rowmap.size() * 4, j.drow)) || (rc = up(colmap.data(), colmap.size() * 4, j.dcol)) || (rc = up(row_starts, (size_t)n_rows * 4, j.drs)) ||
-        (rc = up(col_starts, (size_t)n_cols * 4, j.dcs)) || (rc = up(tile_of.data(), tile_of.size() * 4, j.dtof)) || (rc = up(j.ww.data(), j.ww.size() * 4, j.dww)))
+    if ((rc = c.table(rowmap.data(), rowmap.size() * 4, &j.drow)) || (rc = c.table(colmap.data(), colmap.size() * 4, &j.dcol)) ||
+        (rc = c.table(row_starts, (size_t)n_rows * 4, &j.drs)) || (rc = c.table(col_starts, (size_t)n_cols * 4, &j.dcs)) ||
+        (rc = c.table(tile_of.data(), tile_of.size() * 4, &j.dtof)) || (rc = c.table(j.ww.data(), j.ww.size() * 4, &j.dww)))
         return rc;
     return TD_OK;
 }
 static int blend_enqueue(td_engine* e, const BlendJob& j, float* dcanvas, int C, int Hc, int Wc, int size, int n_cols, const float* dtiles, int accumulate) {
-    hipLaunchKernelGGL(blend_gather_kernel, grid1((size_t)Hc * Wc), dim3(256), 0, e->stream, dtiles, (const float*)j.dww->p, dcanvas, C, Hc, Wc, size,
-                       (const int*)j.drow->p, (const int*)j.dcol->p, (const int*)j.drs->p, (const int*)j.dcs->p, (const int*)j.dtof->p, n_cols, accumulate);
+    hipLaunchKernelGGL(blend_gather_kernel, grid1((size_t)Hc * Wc), dim3(256), 0, e->stream, dtiles, j.dww, dcanvas, C, Hc, Wc, size,
+                       j.drow, j.dcol, j.drs, j.dcs, j.dtof, n_cols, accumulate);
     HIP_TRY(hipGetLastError());
     return TD_OK;
 }
@@ -1670,32 +1726,21 @@ int td_blend_windows(td_engine* e, float* canvas, int C, int Hc, int Wc, int siz
 
 int td_blend_windows_w(td_engine* e, float* canvas, int C, int Hc, int Wc, int size, int n_rows, const int32_t* row_starts, int n_cols,
                        const int32_t* col_starts, int n_tiles, const int32_t* wi, const int32_t* wj, const float* tiles, int accumulate, const float* window) {
-    DevGuard dg_(e->device);
-    hipStream_t st = e->stream;
     BlendJob j;
+    Call c(e);
     int rc;
-    if ((rc = blend_prepare(e, j, C, Hc, Wc, size, n_rows, row_starts, n_cols, col_starts, n_tiles, wi, wj, window))) return rc;
-    std::vector<Buf> hold;
-    const void* dt;
-    if ((rc = to_device(e, tiles, (size_t)n_tiles * C * size * size * 4, hold, &dt))) return rc;
-    const size_t cbytes = (size_t)(C + 1) * Hc * Wc * 4;
-    float* dcanvas = canvas;
-    Buf cstage;
-    const bool cdev = is_device_ptr(canvas);
-    if (!cdev) {
-        cstage.reset(new DevBuf());
-        HIP_TRY(cstage->scratch(e->scratch, cbytes));
-        dcanvas = (float*)cstage->p;
-        if (accumulate) HIP_TRY(hipMemcpyAsync(dcanvas, canvas, cbytes, hipMemcpyHostToDevice, st));
-    }
-    if ((rc = blend_enqueue(e, j, dcanvas, C, Hc, Wc, size, n_cols, (const float*)dt, accumulate))) return rc;
-    if (!cdev) HIP_TRY(hipMemcpyAsync(canvas, dcanvas, cbytes, hipMemcpyDeviceToHost, st));
-    return end_call(e, hold, cdev && is_device_ptr(tiles));
+    if ((rc = blend_prepare(c, j, C, Hc, Wc, size, n_rows, row_starts, n_cols, col_starts, n_tiles, wi, wj, window))) return rc;
+    const float* dt;
+    float* dcanvas;
+    if ((rc = c.in(tiles, (size_t)n_tiles * C * size * size * 4, &dt))) return rc;
+    if ((rc = c.inout(canvas, (size_t)(C + 1) * Hc * Wc * 4, accumulate != 0, &dcanvas))) return rc;   // (a host canvas is read only when it is added to)
+    if ((rc = blend_enqueue(e, j, dcanvas, C, Hc, Wc, size, n_cols, dt, accumulate))) return rc;
+    return c.finish();
 }
 
 int td_gather_regions(td_engine* e, int C, int size, int n_regions, int h, int w, int maxk, const int32_t* desc_host, int n_windows,
                       const uint64_t* window_ptrs_host, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (C + 1 > 8) return fail(TD_ERR_UNSUPPORTED, "C+1 must be <= 8");
     if (n_regions <= 0) return TD_OK;
     if (maxk < 1 || h < 1 || w < 1 || n_windows < 0 || !is_device_ptr(out)) return fail(TD_ERR_ARG, "td_gather_regions: bad shape / host output");
@@ -1710,45 +1755,38 @@ int td_gather_regions(td_engine* e, int C, int size, int n_regions, int h, int w
         HIP_TRY(ww->alloc(hw.size() * 4, false));
         HIP_TRY(hipMemcpy(ww->p, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
     }
-    const size_t dbytes = (size_t)n_regions * maxk * 3 * 4, pbytes = ((size_t)n_windows * 8 + 15) / 16 * 16;
-    Buf stage(new DevBuf());   // window pointers, then the descriptors
-    HIP_TRY(stage->scratch(e->scratch, pbytes + dbytes));
-    unsigned char* stg = (unsigned char*)stage->p;
+    const uint64_t* dptrs;
+    const int32_t* ddesc;
     int rc;
-    if ((rc = upload(e, stg, window_ptrs_host, (size_t)n_windows * 8)) || (rc = upload(e, stg + pbytes, desc_host, dbytes))) return rc;
-    hipLaunchKernelGGL(regions_gather_kernel, dim3((unsigned)(((size_t)h * w + 255) / 256), (unsigned)n_regions), dim3(256), 0, st, (const float* const*)stg,
-                       (const int*)(stg + pbytes), maxk, (const float*)ww->p, out, C, h, w, size);
+    if ((rc = c.table(window_ptrs_host, (size_t)n_windows * 8, &dptrs)) || (rc = c.table(desc_host, (size_t)n_regions * maxk * 3 * 4, &ddesc))) return rc;
+    hipLaunchKernelGGL(regions_gather_kernel, dim3((unsigned)(((size_t)h * w + 255) / 256), (unsigned)n_regions), dim3(256), 0, st, (const float* const*)dptrs,
+                       ddesc, maxk, (const float*)ww->p, out, C, h, w, size);
     HIP_TRY(hipGetLastError());
     // default: complete on return.  Option "async": enqueued; the window tensors are then the caller's to keep valid IN STREAM ORDER (a torch
     // tensor released on the stream the engine runs on is: the allocator reuses its memory for later work of that stream only)
-    std::vector<Buf> hold;
-    hold.push_back(std::move(stage));
-    return end_call(e, hold, true);
+    return c.finish();
 }
 
 int td_blend_normalize(td_engine* e, const float* canvas, int C, int Hc, int Wc, float scale, float* out) {
-    DevGuard dg_(e->device);
-    std::vector<Buf> hold;
-    const void* dc;
+    Call c(e);
+    const float* dc;
+    float* dout;
     int rc;
-    if ((rc = to_device(e, canvas, (size_t)(C + 1) * Hc * Wc * 4, hold, &dc))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, out, (size_t)C * Hc * Wc * 4, hold, &os))) return rc;
-    hipLaunchKernelGGL(blend_normalize_kernel, grid1((size_t)Hc * Wc), dim3(256), 0, e->stream, (const float*)dc, (float*)os.dev, C, Hc * Wc, scale);
+    if ((rc = c.in(canvas, (size_t)(C + 1) * Hc * Wc * 4, &dc)) || (rc = c.out(out, (size_t)C * Hc * Wc * 4, &dout))) return rc;
+    hipLaunchKernelGGL(blend_normalize_kernel, grid1((size_t)Hc * Wc), dim3(256), 0, e->stream, dc, dout, C, Hc * Wc, scale);
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, os))) return rc;
-    return end_call(e, hold, !os.host && is_device_ptr(canvas));
+    return c.finish();
 }
 
 // ---- conditioning rows (sample_diffusion_base.py:11-48 per window, on the GPU)
 struct CondJob {
     std::vector<int32_t> stage;   // 2 n window positions, then the nh histogram floats (one upload)
-    Buf dstage;
-    const void* dgrid = nullptr;
+    const int32_t* dstage = nullptr;
+    const float* dgrid = nullptr;
     CondRowsParams p;
 };
-static int cond_prepare(td_engine* e, CondJob& j, const float* grid, int R, int Cg, int n, const int32_t* pos, const float* means, const float* stds,
-                        const float* hist, int nh, float noise_level, std::vector<Buf>& hold) {
+static int cond_prepare(Call& c, CondJob& j, const float* grid, int R, int Cg, int n, const int32_t* pos, const float* means, const float* stds,
+                        const float* hist, int nh, float noise_level) {
     if (!grid || !pos || !means || !stds || (nh > 0 && !hist)) return fail(TD_ERR_ARG, "td_cond_rows: null argument");
     if (n < 1 || R < 4 || Cg < 4 || nh < 0 || nh > 4096) return fail(TD_ERR_ARG, "td_cond_rows: n >= 1, a grid of at least 4 x 4 cells, 0 <= nh <= 4096");
     for (int i = 0; i < n; ++i)
@@ -1764,17 +1802,15 @@ static int cond_prepare(td_engine* e, CondJob& j, const float* grid, int R, int 
     p.noise_entry = (noise_level - 0.5f) * (float)sqrt(12.0);
     p.R = R; p.Cg = Cg; p.nh = nh; p.n = n;
     int rc;
-    if ((rc = to_device(e, grid, (size_t)7 * R * Cg * 4, hold, &j.dgrid))) return rc;
+    if ((rc = c.in(grid, (size_t)7 * R * Cg * 4, &j.dgrid))) return rc;
     j.stage.resize((size_t)2 * n + nh);
     memcpy(j.stage.data(), pos, (size_t)2 * n * 4);
     if (nh) memcpy(j.stage.data() + (size_t)2 * n, hist, (size_t)nh * 4);
-    j.dstage.reset(new DevBuf());
-    HIP_TRY(j.dstage->scratch(e->scratch, j.stage.size() * 4));
-    return upload(e, j.dstage->p, j.stage.data(), j.stage.size() * 4);
+    return c.table(j.stage.data(), j.stage.size() * 4, &j.dstage);
 }
 static int cond_enqueue(td_engine* e, const CondJob& j, float* out_dev) {
-    const int32_t* d = (const int32_t*)j.dstage->p;
-    hipLaunchKernelGGL(cond_rows_kernel, grid1((size_t)j.p.n * (53 + j.p.nh)), dim3(256), 0, e->stream, (const float*)j.dgrid, (const int*)d,
+    const int32_t* d = j.dstage;
+    hipLaunchKernelGGL(cond_rows_kernel, grid1((size_t)j.p.n * (53 + j.p.nh)), dim3(256), 0, e->stream, j.dgrid, d,
                        (const float*)(d + (size_t)2 * j.p.n), out_dev, j.p);
     HIP_TRY(hipGetLastError());
     return TD_OK;
@@ -1783,25 +1819,24 @@ static int cond_enqueue(td_engine* e, const CondJob& j, float* out_dev) {
 int td_cond_rows(td_engine* e, const float* grid, int grid_rows, int grid_cols, int n, const int32_t* pos_host, const float* means_host, const float* stds_host,
                  const float* hist_host, int n_hist, float noise_level, float* out) {
     if (!e || !out) return fail(TD_ERR_ARG, "td_cond_rows: null argument");
-    DevGuard dg_(e->device);
-    std::vector<Buf> hold;
     CondJob j;
+    Call c(e);
     int rc;
-    if ((rc = cond_prepare(e, j, grid, grid_rows, grid_cols, n, pos_host, means_host, stds_host, hist_host, n_hist, noise_level, hold))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, out, (size_t)n * (53 + n_hist) * 4, hold, &os))) return rc;
-    if ((rc = cond_enqueue(e, j, (float*)os.dev))) return rc;
-    if ((rc = out_finish(e, os))) return rc;
-    return end_call(e, hold, !os.host && is_device_ptr(grid));
+    if ((rc = cond_prepare(c, j, grid, grid_rows, grid_cols, n, pos_host, means_host, stds_host, hist_host, n_hist, noise_level))) return rc;
+    float* dout;
+    if ((rc = c.out(out, (size_t)n * (53 + n_hist) * 4, &dout))) return rc;
+    if ((rc = cond_enqueue(e, j, dout))) return rc;
+    return c.finish();
 }
 
 // ---- one window batch of the grid sampler as ONE call: every host preparation and upload first, then noise -> conditioning rows -> the sampler's
-// lanes -> blend accumulate enqueued back to back on the engine's stream, and one end_call.  The same kernels on the same inputs in the same order as
+// lanes -> blend accumulate enqueued back to back on the engine's stream, and one end of call.  The same kernels on the same inputs in the same order as
 // td_noise_patches + td_cond_rows + td_sample_edm + td_blend_windows, which wait for the stream four times and leave the GPU idle in between.
 int td_sample_grid_batch(td_unet* u, const td_grid_batch* b) {
     if (!u || !b) return fail(TD_ERR_ARG, "td_sample_grid_batch: null argument");
     td_engine* e = u->eng;
-    DevGuard dg_(e->device);
+    NoiseJob nj; CondJob cj; BlendJob bj;
+    Call c(e);
     if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
     const int n = b->n, H = b->H, W = b->W, C = u->cfg.out_channels;
     if (n < 1 || H < 1 || W < 1 || !b->origins_host || !b->sigmas_host || b->n_steps < 1) return fail(TD_ERR_ARG, "td_sample_grid_batch: bad batch description");
@@ -1811,149 +1846,121 @@ int td_sample_grid_batch(td_unet* u, const td_grid_batch* b) {
     if (b->canvas && (H != b->size || W != b->size)) return fail(TD_ERR_ARG, "td_sample_grid_batch: the blend takes square windows of `size`");
     if (u->cond_row_len > 0 && !b->cond_rows && !b->cond_grid) return fail(TD_ERR_ARG, "td_sample_grid_batch: the model takes conditioning rows");
     if (b->cond_grid && !b->cond_rows && 53 + b->n_hist != u->cond_row_len) return fail(TD_ERR_ARG, "td_sample_grid_batch: 53 + n_hist must equal the model's conditioning row length");
-    std::vector<Buf> hold;
-    NoiseJob nj; CondJob cj; BlendJob bj;
     int rc;
-    // a failure past this point may leave uploads from the job structs' host arrays in flight: drain the stream before they go
-    auto bail = [&](int code) { (void)hipStreamSynchronize(e->stream); return code; };
     // host preparation and uploads
-    if ((rc = noise_prepare(e, nj, b->noise_seed, n, b->origins_host, H, W, C, b->tile_h, b->tile_w))) return bail(rc);
-    const void* drows = nullptr;
+    if ((rc = noise_prepare(c, nj, b->noise_seed, n, b->origins_host, H, W, C, b->tile_h, b->tile_w))) return rc;
+    const float* drows = nullptr;
+    float* rows_out = nullptr;
     const bool rows_from_grid = u->cond_row_len > 0 && !b->cond_rows;
     if (rows_from_grid) {
-        if ((rc = cond_prepare(e, cj, b->cond_grid, b->grid_rows, b->grid_cols, n, b->cond_pos_host, b->cond_means_host, b->cond_stds_host, b->hist_host, b->n_hist,
-                               b->noise_level, hold))) return bail(rc);
-        Buf r(new DevBuf());
-        if (r->scratch(e->scratch, (size_t)n * u->cond_row_len * 4) != hipSuccess) return bail(fail(TD_ERR_HIP, "td_sample_grid_batch: scratch allocation"));
-        drows = r->p;
-        hold.push_back(std::move(r));
-    } else if (u->cond_row_len > 0 && (rc = to_device(e, b->cond_rows, (size_t)n * u->cond_row_len * 4, hold, &drows))) return bail(rc);
-    if (b->canvas && (rc = blend_prepare(e, bj, C, b->Hc, b->Wc, b->size, b->n_rows, b->row_starts_host, b->n_cols, b->col_starts_host, n, b->wi_host, b->wj_host))) return bail(rc);
+        if ((rc = cond_prepare(c, cj, b->cond_grid, b->grid_rows, b->grid_cols, n, b->cond_pos_host, b->cond_means_host, b->cond_stds_host, b->hist_host, b->n_hist,
+                               b->noise_level))) return rc;
+        if ((rc = c.scratch((size_t)n * u->cond_row_len * 4, &rows_out))) return rc;
+        drows = rows_out;
+    } else if ((rc = c.in(b->cond_rows, (size_t)n * u->cond_row_len * 4, &drows))) return rc;   // (rows a model without conditional inputs never reads count too)
+    if (b->canvas && (rc = blend_prepare(c, bj, C, b->Hc, b->Wc, b->size, b->n_rows, b->row_starts_host, b->n_cols, b->col_starts_host, n, b->wi_host, b->wj_host))) return rc;
     float* x = b->windows_out;
-    if (!x) {
-        Buf xb(new DevBuf());
-        if (xb->scratch(e->scratch, (size_t)n * C * H * W * 4) != hipSuccess) return bail(fail(TD_ERR_HIP, "td_sample_grid_batch: scratch allocation"));
-        x = (float*)xb->p;
-        hold.push_back(std::move(xb));
-    }
+    if (!x && (rc = c.scratch((size_t)n * C * H * W * 4, &x))) return rc;
     // the GPU work, back to back
-    if ((rc = noise_enqueue(e, nj, n, H, W, C, b->tile_h, b->tile_w, b->noise_scale, x))) return bail(rc);
-    if (rows_from_grid && (rc = cond_enqueue(e, cj, (float*)drows))) return bail(rc);
-    if ((rc = sample_edm_enqueue(u, nullptr, 1.f, n, H, W, b->n_steps, b->sigmas_host, b->sigma_data, (const float*)drows, nullptr, 0, x, hold))) return bail(rc);
-    if (b->canvas && (rc = blend_enqueue(e, bj, b->canvas, C, b->Hc, b->Wc, b->size, b->n_cols, x, b->accumulate))) return bail(rc);
-    return end_call(e, hold, (!b->cond_rows || is_device_ptr(b->cond_rows)) && (!rows_from_grid || is_device_ptr(b->cond_grid)));
+    if ((rc = noise_enqueue(e, nj, n, H, W, C, b->tile_h, b->tile_w, b->noise_scale, x))) return rc;
+    if (rows_from_grid && (rc = cond_enqueue(e, cj, rows_out))) return rc;
+    if ((rc = sample_edm_enqueue(u, edm_args(n, H, W, b->n_steps, b->sigmas_host, b->sigma_data, drows, nullptr, 0, x), c))) return rc;
+    if (b->canvas && (rc = blend_enqueue(e, bj, b->canvas, C, b->Hc, b->Wc, b->size, b->n_cols, x, b->accumulate))) return rc;
+    return c.finish();
 }
 
 // ---- output composition
 int td_resample2d(td_engine* e, const float* in, int C, int Hin, int Win, int Hout, int Wout, const int32_t* iy, const float* wy, int Ky,
                   const int32_t* ix, const float* wx, int Kx, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (C < 1 || Hin < 1 || Win < 1 || Hout < 1 || Wout < 1 || Ky < 1 || Kx < 1) return fail(TD_ERR_ARG, "td_resample2d: bad geometry");
     for (int i = 0; i < Hout * Ky; ++i) if (iy[i] < 0 || iy[i] >= Hin) return fail(TD_ERR_ARG, "td_resample2d: row tap out of range");
     for (int i = 0; i < Wout * Kx; ++i) if (ix[i] < 0 || ix[i] >= Win) return fail(TD_ERR_ARG, "td_resample2d: column tap out of range");
     hipStream_t st = e->stream;
-    std::vector<Buf> hold;
-    const void *din, *diy, *dwy, *dix, *dwx;
+    const float *din, *dwy, *dwx;
+    const int32_t *diy, *dix;
+    float *dout, *tmp;
     int rc;
-    if ((rc = to_device(e, in, (size_t)C * Hin * Win * 4, hold, &din)) || (rc = to_device(e, iy, (size_t)Hout * Ky * 4, hold, &diy)) ||
-        (rc = to_device(e, wy, (size_t)Hout * Ky * 4, hold, &dwy)) || (rc = to_device(e, ix, (size_t)Wout * Kx * 4, hold, &dix)) ||
-        (rc = to_device(e, wx, (size_t)Wout * Kx * 4, hold, &dwx))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, out, (size_t)C * Hout * Wout * 4, hold, &os))) return rc;
-    Buf tmp(new DevBuf());
-    HIP_TRY(tmp->scratch(e->scratch, (size_t)C * Hin * Wout * 4));
-    hipLaunchKernelGGL(resample_rows_kernel, grid1((size_t)C * Hin * Wout), dim3(256), 0, st, (const float*)din, (float*)tmp->p, C, Hin, Win, Wout, (const int*)dix, (const float*)dwx, Kx);
-    hipLaunchKernelGGL(resample_cols_kernel, grid1((size_t)C * Hout * Wout), dim3(256), 0, st, (const float*)tmp->p, (float*)os.dev, C, Hin, Hout, Wout, (const int*)diy, (const float*)dwy, Ky);
+    if ((rc = c.in(in, (size_t)C * Hin * Win * 4, &din)) || (rc = c.table(iy, (size_t)Hout * Ky * 4, &diy)) || (rc = c.table(wy, (size_t)Hout * Ky * 4, &dwy)) ||
+        (rc = c.table(ix, (size_t)Wout * Kx * 4, &dix)) || (rc = c.table(wx, (size_t)Wout * Kx * 4, &dwx)) || (rc = c.out(out, (size_t)C * Hout * Wout * 4, &dout)) ||
+        (rc = c.scratch((size_t)C * Hin * Wout * 4, &tmp))) return rc;
+    hipLaunchKernelGGL(resample_rows_kernel, grid1((size_t)C * Hin * Wout), dim3(256), 0, st, din, tmp, C, Hin, Win, Wout, dix, dwx, Kx);
+    hipLaunchKernelGGL(resample_cols_kernel, grid1((size_t)C * Hout * Wout), dim3(256), 0, st, (const float*)tmp, dout, C, Hin, Hout, Wout, diy, dwy, Ky);
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, os))) return rc;
-    hold.push_back(std::move(tmp));
-    return end_call(e, hold, !os.host && is_device_ptr(in));
+    return c.finish();
 }
 
 int td_residual_plus(td_engine* e, const float* packed, const float* lowres_up, int Hp, int Wp, float res_mean, float res_std, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (!is_device_ptr(packed) || !is_device_ptr(lowres_up) || !is_device_ptr(out)) return fail(TD_ERR_ARG, "td_residual_plus: device buffers only");
     hipLaunchKernelGGL(residual_plus_kernel, grid1((size_t)Hp * Wp), dim3(256), 0, e->stream, packed, lowres_up, out, Hp * Wp, res_mean, res_std);
     HIP_TRY(hipGetLastError());
-    std::vector<Buf> none;
-    return end_call(e, none, true);
+    return c.finish();
 }
 
 int td_elev_finish(td_engine* e, const float* packed, const float* lowres_up, int Hp, int Wp, int oi, int oj, int h, int w, float res_mean, float res_std, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (!is_device_ptr(packed) || !is_device_ptr(lowres_up) || !is_device_ptr(out)) return fail(TD_ERR_ARG, "td_elev_finish: device buffers only");
     if (oi < 0 || oj < 0 || oi + h > Hp || oj + w > Wp) return fail(TD_ERR_ARG, "td_elev_finish: crop outside the window");
     hipLaunchKernelGGL(elev_finish_kernel, grid1((size_t)h * w), dim3(256), 0, e->stream, packed, lowres_up, out, Hp, Wp, oi, oj, h, w, res_mean, res_std);
     HIP_TRY(hipGetLastError());
-    std::vector<Buf> none;
-    return end_call(e, none, true);
+    return c.finish();
 }
 
 int td_ddim_cfg_step(td_engine* e, const float* latent, const float* pred_uncond, const float* pred_cond, int64_t n, float guidance_scale, float alpha_t,
                      float alpha_prev, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (n < 1 || !(alpha_t > 0.f) || !(alpha_t <= 1.f) || !(alpha_prev > 0.f) || !(alpha_prev <= 1.f)) return fail(TD_ERR_ARG, "td_ddim_cfg_step: bad arguments");
     if (!is_device_ptr(latent) || !is_device_ptr(pred_uncond) || !is_device_ptr(pred_cond) || !is_device_ptr(out)) return fail(TD_ERR_ARG, "td_ddim_cfg_step: device buffers only");
     // the scheduler's scalars in fp32 from the (fp32) cumulative alphas, as torch computes alpha ** 0.5 on 0-d fp32 tensors
     hipLaunchKernelGGL(ddim_cfg_step_kernel, grid1((size_t)n), dim3(256), 0, e->stream, latent, pred_uncond, pred_cond, out, (size_t)n, guidance_scale,
                        sqrtf(1.f - alpha_t), sqrtf(alpha_t), sqrtf(alpha_prev), sqrtf(1.f - alpha_prev));
     HIP_TRY(hipGetLastError());
-    std::vector<Buf> none;
-    return end_call(e, none, true);
+    return c.finish();
 }
 
 int td_climate_finish(td_engine* e, const float* feats, int Hs, int Ws, const float* elev, int i1, int j1, int h, int w, float S, int ci1, int cj1, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (!is_device_ptr(feats) || !is_device_ptr(elev) || !is_device_ptr(out)) return fail(TD_ERR_ARG, "td_climate_finish: device buffers only");
     if (Hs < 1 || Ws < 1 || h < 1 || w < 1 || !(S > 0.f)) return fail(TD_ERR_ARG, "td_climate_finish: bad geometry");
     hipLaunchKernelGGL(climate_finish_kernel, grid1((size_t)h * w), dim3(256), 0, e->stream, feats, elev, out, Hs, Ws, i1, j1, h, w, S, ci1, cj1);
     HIP_TRY(hipGetLastError());
-    std::vector<Buf> none;
-    return end_call(e, none, true);
+    return c.finish();
 }
 
 // ---- synthetic conditioning map channel
 int td_perlin_map(td_engine* e, int rows, int cols, int i1, int j1, int seed, float frequency, int octaves, float lacunarity, float gain,
                   const float* src_quantiles, const float* dst_quantiles, int n_quantiles, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (rows < 1 || cols < 1 || octaves < 1 || octaves > 16 || n_quantiles < 2) return fail(TD_ERR_ARG, "td_perlin_map: bad arguments");
-    std::vector<Buf> hold;
-    const void *ds, *dd;
+    const float *ds, *dd;
+    float* dout;
     int rc;
-    if ((rc = to_device(e, src_quantiles, (size_t)n_quantiles * 4, hold, &ds)) || (rc = to_device(e, dst_quantiles, (size_t)n_quantiles * 4, hold, &dd))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, out, (size_t)rows * cols * 4, hold, &os))) return rc;
-    hipLaunchKernelGGL(perlin_map_kernel, grid1((size_t)rows * cols), dim3(256), 0, e->stream, (float*)os.dev, rows, cols, i1, j1, seed, frequency, octaves, lacunarity, gain,
-                       (const float*)ds, (const float*)dd, n_quantiles);
+    if ((rc = c.in(src_quantiles, (size_t)n_quantiles * 4, &ds)) || (rc = c.in(dst_quantiles, (size_t)n_quantiles * 4, &dd)) || (rc = c.out(out, (size_t)rows * cols * 4, &dout))) return rc;
+    hipLaunchKernelGGL(perlin_map_kernel, grid1((size_t)rows * cols), dim3(256), 0, e->stream, dout, rows, cols, i1, j1, seed, frequency, octaves, lacunarity, gain, ds, dd, n_quantiles);
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, os))) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return TD_OK;
+    return c.finish(true);
 }
 
 // ---- generic attention (row N1): softmax(scale * Q K^T) V on the MFMA kernel
 int td_attention(td_engine* e, const float* q, const float* k, const float* v, int B, int H, int Lq, int Lk, int D, float scale, int normalize, float* out) {
-    DevGuard dg_(e->device);
+    Call c(e);
     if (B < 1 || H < 1 || Lq < 1 || Lk < 1 || D < 1 || D > 160) return fail(TD_ERR_ARG, "td_attention: 1 <= D <= 160, positive sizes");
     hipStream_t st = e->stream;
-    std::vector<Buf> hold;
-    const void *dq, *dk, *dv;
+    const float *dq, *dk, *dv;
+    float* dout;
     int rc;
-    if ((rc = to_device(e, q, (size_t)B * H * Lq * D * 4, hold, &dq)) || (rc = to_device(e, k, (size_t)B * H * Lk * D * 4, hold, &dk)) ||
-        (rc = to_device(e, v, (size_t)B * H * Lk * D * 4, hold, &dv))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, out, (size_t)B * H * Lq * D * 4, hold, &os))) return rc;
+    if ((rc = c.in(q, (size_t)B * H * Lq * D * 4, &dq)) || (rc = c.in(k, (size_t)B * H * Lk * D * 4, &dk)) || (rc = c.in(v, (size_t)B * H * Lk * D * 4, &dv)) ||
+        (rc = c.out(out, (size_t)B * H * Lq * D * 4, &dout))) return rc;
     size_t qn, kn, vn;
     const size_t tot = attn_workspace_elems(B, H, Lq, Lk, D, &qn, &kn, &vn);
     Buf ws(new DevBuf());
     HIP_TRY(ws->alloc(tot * 2, false));
     __bf16 *Qp = (__bf16*)ws->p, *Kp = Qp + qn, *Vt = Kp + kn;
     const AttnStrides sq = {(long)H * Lq * D, (long)Lq * D, (long)D, 1L}, sk = {(long)H * Lk * D, (long)Lk * D, (long)D, 1L};
-    HIP_TRY(attn_pack<float>((const float*)dq, (const float*)dk, (const float*)dv, sq, sk, sk, B, H, Lq, Lk, D, normalize, scale, Qp, Kp, Vt, st));
-    HIP_TRY(attn_mfma(Qp, Kp, Vt, (float*)os.dev, nullptr, sq, B, H, Lq, Lk, D, st));
-    if ((rc = out_finish(e, os))) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    return TD_OK;
+    HIP_TRY(attn_pack<float>(dq, dk, dv, sq, sk, sk, B, H, Lq, Lk, D, normalize, scale, Qp, Kp, Vt, st));
+    HIP_TRY(attn_mfma(Qp, Kp, Vt, dout, nullptr, sq, B, H, Lq, Lk, D, st));
+    return c.finish(true);
 }
 
 }  // extern "C"
@@ -1979,34 +1986,8 @@ static bool ae_ignored(const std::string& n) {
     return (n.size() > eg.size() && n.compare(n.size() - eg.size(), eg.size(), eg) == 0) || n == "logvar" || n.rfind("encoder.logvar_", 0) == 0;
 }
 
-// option "profile": HIP events around the kernels of ae_kernels.hip, accumulated with the U-Net's non-conv kernels (td_engine_profile_read: other_ms) under
-// their own labels; as in run_unet the read-out waits for the stream, so a profiled call is not enqueue-only
-struct AeProf {
-    td_engine* e;
-    bool on;
-    std::vector<hipEvent_t> evs;
-    std::vector<std::string> labels;
-    explicit AeProf(td_engine* e_) : e(e_), on(e_->option("profile", 0) != 0) {}
-    void mark(const char* label) {   // call before and after a launch; the label of the first call counts
-        if (!on) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) return;
-        (void)hipEventRecord(ev, e->stream);
-        evs.push_back(ev);
-        if (evs.size() & 1) labels.push_back(label);
-    }
-    ~AeProf() {
-        if (evs.empty()) return;
-        (void)hipStreamSynchronize(e->stream);
-        for (size_t i = 0; i + 1 < evs.size(); i += 2) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
-            auto& po = e->prof_ops[labels[i / 2]]; po.first += ms; po.second++;
-            e->prof_other_ms += ms; e->prof_other_launches++;
-        }
-        for (auto ev : evs) (void)hipEventDestroy(ev);
-    }
-};
+// (option "profile": the kernels of ae_kernels.hip are timed by a ProfScope under their own labels and counted with the U-Net's non-conv kernels,
+// td_engine_profile_read: other_ms)
 
 extern "C" {
 
@@ -2079,7 +2060,7 @@ int td_ae_preencode(td_ae* a, int n_src, int H, int W, const float* x, float mea
     if (!a || !x || !means || !logvars) return fail(TD_ERR_ARG, "td_ae_preencode: null argument");
     td_engine* e = a->eng;
     td_unet* u = a->enc.get();
-    DevGuard dg_(e->device);
+    Call c(e);
     if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
     if (n_src < 1 || H < 1 || W < 1) return fail(TD_ERR_ARG, "td_ae_preencode: bad geometry");
     if (dihedral && H != W) return fail(TD_ERR_UNSUPPORTED, "td_ae_preencode: the dihedral form needs H == W");
@@ -2089,53 +2070,46 @@ int td_ae_preencode(td_ae* a, int n_src, int H, int W, const float* x, float mea
     if (rc) return rc;
     const int h = H / s, w = W / s;
     hipStream_t st = e->stream;
-    std::vector<Buf> hold;
-    const void* dx;
-    if ((rc = to_device(e, x, (size_t)n_src * C * H * W * 4, hold, &dx))) return rc;
-    OutStage om, ol, op;
+    const float* dx;
+    float *dmeans, *dlogvars;
+    void* dpacked = nullptr;
     const size_t lat = (size_t)n * LD * h * w;
-    if ((rc = out_device(e, means, lat * 4, hold, &om)) || (rc = out_device(e, logvars, lat * 4, hold, &ol))) return rc;
-    op.dev = nullptr; op.host = nullptr; op.bytes = 0;
-    if (packed_f16 && (rc = out_device(e, packed_f16, lat * 2 * 2, hold, &op))) return rc;
+    if ((rc = c.in(x, (size_t)n_src * C * H * W * 4, &dx)) || (rc = c.out(means, lat * 4, &dmeans)) || (rc = c.out(logvars, lat * 4, &dlogvars))) return rc;
+    if (packed_f16 && (rc = c.out(packed_f16, lat * 2 * 2, &dpacked))) return rc;
     AeSrc src;
-    src.x = (const float*)dx; src.C = C; src.H = H; src.W = W; src.dihedral = dihedral ? 1 : 0; src.mean = mean; src.std = std;
-    AeProf prof(e);
-    prof.mark("ae_prep_input");
+    src.x = dx; src.C = C; src.H = H; src.W = W; src.dihedral = dihedral ? 1 : 0; src.mean = mean; src.std = std;
+    ProfScope prof(e);
+    prof.begin();
     TD_DISPATCH_T(u, hipLaunchKernelGGL(ae_prep_input_kernel<T_>, grid1((size_t)n * H * W), dim3(256), 0, st, src, (T_*)pl->xin, n, u->chunk));
-    prof.mark("ae_prep_input");
+    prof.end("ae_prep_input");
     HIP_TRY(hipGetLastError());
     if ((rc = run_unet(u, *pl, 0))) return rc;
-    prof.mark("ae_latent_head");
-    hipLaunchKernelGGL(ae_latent_head_kernel, grid1((size_t)n * h * w), dim3(256), 0, st, (const float*)pl->F, 8, src, a->dir, n, a->L, h, w, s, (float*)om.dev, (float*)ol.dev,
-                       (_Float16*)op.dev);
-    prof.mark("ae_latent_head");
+    prof.begin();
+    hipLaunchKernelGGL(ae_latent_head_kernel, grid1((size_t)n * h * w), dim3(256), 0, st, (const float*)pl->F, 8, src, a->dir, n, a->L, h, w, s, dmeans, dlogvars, (_Float16*)dpacked);
+    prof.end("ae_latent_head");
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, om)) || (rc = out_finish(e, ol))) return rc;
-    if (packed_f16 && (rc = out_finish(e, op))) return rc;
-    return end_call(e, hold, !om.host && !ol.host && !op.host && is_device_ptr(x));
+    return c.finish();
 }
 
 int td_ae_postencode(td_ae* a, int64_t numel, const float* means, const float* logvars, const float* eps, float* z) {
     if (!a || !means || !logvars || !eps || !z || numel < 1) return fail(TD_ERR_ARG, "td_ae_postencode: bad arguments");
     td_engine* e = a->eng;
-    DevGuard dg_(e->device);
-    std::vector<Buf> hold;
-    const void *dm, *dl, *de;
+    Call c(e);
+    const float *dm, *dl, *de;
+    float* dz;
     int rc;
-    if ((rc = to_device(e, means, (size_t)numel * 4, hold, &dm)) || (rc = to_device(e, logvars, (size_t)numel * 4, hold, &dl)) || (rc = to_device(e, eps, (size_t)numel * 4, hold, &de))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, z, (size_t)numel * 4, hold, &os))) return rc;
-    hipLaunchKernelGGL(ae_postencode_kernel, grid1((size_t)numel), dim3(256), 0, e->stream, (const float*)dm, (const float*)dl, (const float*)de, (float*)os.dev, (size_t)numel);
+    if ((rc = c.in(means, (size_t)numel * 4, &dm)) || (rc = c.in(logvars, (size_t)numel * 4, &dl)) || (rc = c.in(eps, (size_t)numel * 4, &de)) ||
+        (rc = c.out(z, (size_t)numel * 4, &dz))) return rc;
+    hipLaunchKernelGGL(ae_postencode_kernel, grid1((size_t)numel), dim3(256), 0, e->stream, dm, dl, de, dz, (size_t)numel);
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, os))) return rc;
-    return end_call(e, hold, !os.host && is_device_ptr(means) && is_device_ptr(logvars) && is_device_ptr(eps));
+    return c.finish();
 }
 
 int td_ae_decode(td_ae* a, int n, int h, int w, const float* z, float std, float mean, float* out) {
     if (!a || !z || !out) return fail(TD_ERR_ARG, "td_ae_decode: null argument");
     td_engine* e = a->eng;
     td_unet* u = a->dec.get();
-    DevGuard dg_(e->device);
+    Call c(e);
     if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
     if (n < 1 || h < 1 || w < 1) return fail(TD_ERR_ARG, "td_ae_decode: bad geometry");
     Plan* pl;
@@ -2143,25 +2117,22 @@ int td_ae_decode(td_ae* a, int n, int h, int w, const float* z, float std, float
     if (rc) return rc;
     const int LD = a->L + a->D, s = a->sdown, H = h * s, W = w * s, Co = a->cfg.out_channels;
     hipStream_t st = e->stream;
-    std::vector<Buf> hold;
-    const void* dz;
-    if ((rc = to_device(e, z, (size_t)n * LD * h * w * 4, hold, &dz))) return rc;
-    OutStage os;
-    if ((rc = out_device(e, out, (size_t)n * Co * H * W * 4, hold, &os))) return rc;
+    const float* dz;
+    float* dout;
+    if ((rc = c.in(z, (size_t)n * LD * h * w * 4, &dz)) || (rc = c.out(out, (size_t)n * Co * H * W * 4, &dout))) return rc;
     // z + ones channel -> NHWC storage type (edm_autoencoder.py:137): the U-Net's input staging as it is
-    AeProf prof(e);
-    prof.mark("ae_decode_head");
-    TD_DISPATCH_T(u, hipLaunchKernelGGL(prep_input_kernel<T_>, grid1((size_t)n * h * w), dim3(256), 0, st, (const float*)dz, (T_*)pl->xin, n, LD, h * w, u->chunk, 1.f, LD));
-    prof.mark("ae_decode_head");
+    ProfScope prof(e);
+    prof.begin();
+    TD_DISPATCH_T(u, hipLaunchKernelGGL(prep_input_kernel<T_>, grid1((size_t)n * h * w), dim3(256), 0, st, dz, (T_*)pl->xin, n, LD, h * w, u->chunk, 1.f, LD));
+    prof.end("ae_decode_head");
     HIP_TRY(hipGetLastError());
     if ((rc = run_unet(u, *pl, 0))) return rc;
-    prof.mark("ae_decode_finish");
-    hipLaunchKernelGGL(ae_decode_finish_kernel, grid1((size_t)n * H * W), dim3(256), 0, st, (const float*)pl->F, 8, (const float*)dz, a->dir, n, Co, a->L, H, W, s,
-                       (std != 1.f || mean != 0.f) ? 1 : 0, std, mean, (float*)os.dev);
-    prof.mark("ae_decode_finish");
+    prof.begin();
+    hipLaunchKernelGGL(ae_decode_finish_kernel, grid1((size_t)n * H * W), dim3(256), 0, st, (const float*)pl->F, 8, dz, a->dir, n, Co, a->L, H, W, s,
+                       (std != 1.f || mean != 0.f) ? 1 : 0, std, mean, dout);
+    prof.end("ae_decode_finish");
     HIP_TRY(hipGetLastError());
-    if ((rc = out_finish(e, os))) return rc;
-    return end_call(e, hold, !os.host && is_device_ptr(z));
+    return c.finish();
 }
 
 }  // extern "C"
