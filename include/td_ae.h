@@ -62,6 +62,12 @@ int td_ae_postencode(td_ae* ae, int64_t numel, const float* means, const float* 
  * direct_skips[d] is the nearest-neighbour upsampling of latent channel L + d.  Then out * std + mean (a multiply and an add, rounded separately, as
  * torch's `y * std + mean`); std = 1 with mean = 0 leaves the decoder's output as it is.  Host or device; enqueue-only under "async" for device pointers. */
 int td_ae_decode(td_ae* ae, int n, int h, int w, const float* z, float std, float mean, float* out);
+/* Test facility: td_unet_read_activation on one of the two stacks, as the last td_ae_preencode (stack 1, the encoder) or td_ae_decode (stack 2, the
+ * decoder) of that batch and map left it.  H, W: that stack's own input map, the image for the encoder (n = 8 * n_src in the dihedral form), the
+ * latent for the decoder.  label: a conv or attention op's profile label, "sumsq:<label>", or "@xin" (the staged NHWC input, every channel of its
+ * K chunk).  The labels of what these stacks do not have -- "@emb", "@cvec", "@emb:rows", "@cvec:rows" (no embedding: the modulation is one shared row
+ * of ones) and "@x", "@m1", "@m2", "@xt" (no sampler state) -- are refused with TD_ERR_ARG, as is any other stack.  Always waits for the stream. */
+int td_ae_read_activation(td_ae* ae, int stack, int n, int H, int W, const char* label, float* out_host, int64_t capacity, int32_t dims[4]);
 
 #ifdef __cplusplus
 }

@@ -146,6 +146,7 @@ _AE_SIGS = {
     "td_ae_preencode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_int, _P, _P, _P]),
     "td_ae_postencode": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "td_ae_decode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, _P]),
+    "td_ae_read_activation": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int32 * 4)]),
 }
 AE_EXPORTS = tuple(k for k in _AE_SIGS if k.startswith("td_ae_"))
 _AE_LIB = Library("libtd_engine.so", _AE_SIGS, "td_last_error", "td_engine")

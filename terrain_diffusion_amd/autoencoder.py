@@ -222,6 +222,18 @@ class EDMAutoencoder:
             return out, torch.as_tensor(self._state["logvar"]).to(torch.float32).reshape(-1, 1, 1, 1)
         return out
 
+    def read_activation(self, stack, n, H, W, label, max_elems=1 << 26):
+        """Debug/test: what `EDMUnet2D.read_activation` gives, on one of the two stacks (1 the encoder, 2 the decoder), from the last preencode / decode
+        with this batch and map.  H, W are that stack's own input map (the image for the encoder, the latent for the decoder); `label` is a conv or
+        attention op, "sumsq:<label>" or "@xin".  NCHW fp32 (host)."""
+        import numpy as np
+        self._need()
+        buf = np.empty(max_elems, dtype=np.float32)
+        dims = (C.c_int32 * 4)()
+        check(lib().td_ae_read_activation(self._h, int(stack), n, H, W, label.encode(), C.c_void_p(buf.ctypes.data), buf.size, C.byref(dims)))
+        shape = tuple(dims)
+        return torch.from_numpy(buf[:int(np.prod(shape))].reshape(shape).copy())
+
     def preencode_dihedral(self, residual, residual_mean=0.0, residual_std=1.1678):
         """The 8 dihedral views of one chunk through preencode in one engine call -> (means, logvars, packed): fp32 (8, L + D, h, w) twice and
         cat(means, logvars) as float16."""

@@ -2135,4 +2135,16 @@ int td_ae_decode(td_ae* a, int n, int h, int w, const float* z, float std, float
     return c.finish();
 }
 
+int td_ae_read_activation(td_ae* a, int stack, int n, int H, int W, const char* label, float* out_host, int64_t capacity, int32_t dims[4]) {
+    if (!a || !label || !out_host || !dims) return fail(TD_ERR_ARG, "td_ae_read_activation: null argument");
+    if (stack != 1 && stack != 2) return fail(TD_ERR_ARG, "td_ae_read_activation: stack is 1 (encoder) or 2 (decoder)");
+    if (n < 1 || H < 1 || W < 1) return fail(TD_ERR_ARG, "td_ae_read_activation: bad geometry");
+    // a kind != 0 plan has no embedding or cvec buffer (its modulation is d_ones) and 16 bytes of sampler state (build_plan: xbytes)
+    for (const char* none : {"@emb", "@cvec", "@emb:rows", "@cvec:rows", "@x", "@m1", "@m2", "@xt"})
+        if (!strcmp(label, none)) return fail(TD_ERR_ARG, std::string("td_ae_read_activation: the autoencoder's stacks have no ") + label);
+    td_unet* u = stack == 1 ? a->enc.get() : a->dec.get();
+    if (!u->finalized) return fail(TD_ERR_STATE, "finalize first");
+    return td_unet_read_activation(u, n, H, W, label, out_host, capacity, dims);
+}
+
 }  // extern "C"

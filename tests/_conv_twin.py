@@ -1,6 +1,7 @@
 """Host model ("twin") of every fused conv op of the U-Net engine, in plain torch float64, and the element-wise criterion it is held to.
 
-What it is.  `describe(cfg)` walks `oracle.unet.build_plan(cfg)` and restates, op by op, what `build_plan` / `finalize` in
+What it is.  `describe_ae(cfg, kind)` is the same for the two stacks of the EDMAutoencoder (tests/_ae_twin.py's plan; tests/test_ae_conv_ops_cpu.py holds both
+op lists to csrc/model_graph.h field for field).  `describe(cfg)` walks `oracle.unet.build_plan(cfg)` and restates, op by op, what `build_plan` / `finalize` in
 `terrain_diffusion_amd/csrc/engine.hip` emit: the K-segments of each fused conv (source op, real channels, taps, resample, transform), the weight
 slice and its `mul` factor, the epilogue and the output type.  `Twin.eval(op, stored, cvec)` computes ONE op in float64 FROM THE TENSORS THE
 ENGINE STORED (the outputs of the producing ops as `read_activation` returns them), so an error cannot hide behind the layers in front of it or be
@@ -19,8 +20,14 @@ The model of one op
             modulated mp_silu), so that s is the scale of the K sum AT THE OUTPUT; and the three parts of E.
 
 The slack E (three named parts; u = 2^-24)
-  accumulation   E_acc = C_ACC * u * sqrt(K / 16) * sqrt(s0^2 + v^2), pushed through the epilogue (s0 = s before that).  The matrix core sums 16 products
-                 (4 in fp32 mode: K / 4, C_ACC32) and adds that to its fp32 accumulator: K / 16 roundings, each relative to the running sum -- whose random part
+  accumulation   E_acc = C_ACC * u * sqrt(S) * sqrt(s0^2 + v^2), pushed through the epilogue (s0 = s before that).  The matrix core sums 16 products
+                 (4 in fp32 mode, C_ACC32) and adds that to its fp32 accumulator: S roundings, S = `acc_steps` = sum over the K-segments of taps * ceil(C / 16),
+                 which is K / 16 for every block conv.  (First stated as K / 16 for all ops.  The autoencoder's 3x3 input conv of 1 + 1 or 2 + 1 channels showed
+                 that to be wrong where a few real channels sit in a padded chunk: 9 accumulate steps, not 18 / 16, and an emulation ratio of 3.42 / 3.72 in fp16
+                 under the K / 16 form, 1.5 / 1.3 over S (the same errors over the right count); the count was corrected, C_ACC was not touched.  The U-Net's input conv, 5 + 1 channels, has
+                 S = 9 against 54 / 16 as well, and `decoder_conv` S = 1.  For that one U-Net op the corrected count LOOSENS the criterion its GPU arms already held:
+                 E_acc of `enc.*_conv` grows by sqrt(9 / 3.375) = 1.63 in bf16 and fp16 and by sqrt(18 / 13.5) = 1.15 in fp32, every other U-Net op keeps its S.  The basis is
+                 the count itself -- one rounding per tap per real channel group, none for the all-zero groups -- and the CPU emulation, not a GPU measurement.)  Each rounding is relative to the running sum -- whose random part
                  scales with s0 and whose coherent part with |v|.  With s0 alone (the form first tried) the worst emulation ratios come from 1x1 convs of
                  pixel-normed inputs, whose terms share a sign (3.9 - 4.5 against 2.0 - 2.3 with the v term), and the constant they force makes
                  E_acc / half_ulp > 0.5 on the K = 1536 * 9 layers in fp16: the model was tightened, not the condition.
@@ -52,6 +59,8 @@ these ratios (worst over the tiny attention model in bf16 / fp16 / fp32 and the 
 with the threading of the sums):
     accumulation, 16-bit   worst |v32 - v64| / (u sqrt(K / 16) sqrt(s0^2 + v^2)) = 2.26     x 8 (the MFMA's summation tree is not the CPU's) -> C_ACC   = 20
     accumulation, fp32     worst, K / 4                                           = 1.74     x 8                                              -> C_ACC32 = 16
+                           (as recorded when the constants were fixed, over K / 16 resp. K / 4.  Over S = `acc_steps`, which differs for the input conv only, the same four
+                           runs give 1.99 / 1.84 / 2.07 in bf16 / fp16 / base bf16 and 1.74 in fp32: the constants keep their factor of 8.)
     epilogue               worst |epi32 - epi64| / (u m (1 + |t| sig(t)))         = 4.93     x 4                                              -> C_EPI   = 22
     prologue               C_PRO = 6 from the ISA's statements as above; the emulation's activation IS the twin's, so it has no ratio of its own.  For the
                            record: fp32 form against float64, |a32 - a64| / (u |a| (1 + |t| sig(t))) = 4.9 (transform 1), 6.0 (transform 2, fp32 sums).
@@ -61,6 +70,8 @@ The two conditions that keep the criterion honest, both asserted by `check_op`: 
 median over its elements of (E_acc + E_epi + E_pro) / half_ulp_T(ref) is <= 0.5 (elements with |ref| < 2^-6 rms(ref) are left out of THAT STATISTIC only:
 near zero the half-ulp vanishes while E does not).  Largest median per run: CPU emulation 0.04 (base bf16, enc.64x64_block2.conv_res0), 0.02 (tiny bf16),
 0.19 (tiny fp16, dec.128x128_block0.conv_res0); MI355X 0.02 - 0.04 in every bf16 arm, 0.32 / 0.38 in the fp16 arms (n = 64 / n = 1).
+The autoencoder's stacks (tests/test_ae_conv_ops_cpu.py has their ratio table, tests/test_ae_conv_ops_gpu.py the arms): CPU emulation 0.016 (released bf16), 0.169
+(released fp16, encoder.enc.64x64_down.conv_res0); MI355X 0.006 - 0.041 in every bf16 arm, 0.118 / 0.222 / 0.215 in the fp16 arms (decoder / encoder / dihedral encoder).
 What else the MI355X showed is in DESIGN.md, "How the conv kernels are checked".
 
 Run as a script on a GPU box for a per-op table of one forward:  python tests/_conv_twin.py [bf16|fp16|fp32] [n]
@@ -133,77 +144,145 @@ def fold_host(w, gain=1.0):
 
 
 # ------------------------------------------------------------------------------------------------ the plan
-def describe(cfg):
-    """Every fused conv op the engine emits for `cfg`, in execution order (mirror of build_plan / finalize in engine.hip).
-    Sizes are relative: `shift` = log2 of the downsampling of the op's map against the network input."""
-    plan = build_plan(cfg)
-    t = cfg.get("concat_balance", 0.3)
-    ops, coff = [], 0
-    seg = lambda src, C, taps, rs, xf, wname, cin_tot, cin_off, scale=(1.0, 1.0), mul=(1.0, 1.0): dict(
-        src=src, C=C, taps=taps, resample=rs, xform=xf, wname=wname, cin_tot=cin_tot, cin_off=cin_off, scale64=scale[0], scale32=scale[1], mul64=mul[0], mul32=mul[1])
+class _Graph:
+    """the op list under construction: what `describe` (the U-Net) and `describe_ae` (the autoencoder's two stacks) have in common.  One op is a dict
+    label / segs / cout / shift / epi / cvec_off / res / clip / out_f32 / sumsq / K; one K-segment a dict src / C / taps / resample / xform / wname / gain (name
+    of the scalar parameter folded into the weight, or None) / cin_tot / cin_off / scale64 / scale32 / mul64 / mul32."""
 
-    def op(label, segs, cout, shift, epi="plain", cvec_off=-1, res=None, clip=0.0, out_f32=False, sumsq=False):
-        ops.append(dict(label=label, segs=segs, cout=cout, shift=shift, epi=epi, cvec_off=cvec_off, res=res, clip=clip, out_f32=out_f32, sumsq=sumsq,
-                        K=sum(s["C"] * s["taps"] for s in segs)))
+    def __init__(self, modulated):
+        self.ops, self.modulated, self.coff = [], modulated, 0
+
+    @staticmethod
+    def seg(src, C, taps, rs, xf, wname, cin_tot, cin_off, scale=(1.0, 1.0), mul=(1.0, 1.0), gain=None):
+        return dict(src=src, C=C, taps=taps, resample=rs, xform=xf, wname=wname, gain=gain, cin_tot=cin_tot, cin_off=cin_off, scale64=scale[0], scale32=scale[1],
+                    mul64=mul[0], mul32=mul[1])
+
+    def op(self, label, segs, cout, shift, epi="plain", cvec_off=-1, res=None, clip=0.0, out_f32=False, sumsq=False):
+        self.ops.append(dict(label=label, segs=segs, cout=cout, shift=shift, epi=epi, cvec_off=cvec_off, res=res, clip=clip, out_f32=out_f32, sumsq=sumsq,
+                             K=sum(s["C"] * s["taps"] for s in segs)))
         return label
 
-    def attn(n, o, cout, shift, sumsq):
+    def cvec_off(self, b):
+        """a modulated block (the U-Net) owns `cout` columns of @cvec; the autoencoder's blocks all read the one row of ones from its start"""
+        if not self.modulated:
+            return 0
+        b["cvec_off"] = self.coff
+        self.coff += b["cout"]
+        return b["cvec_off"]
+
+    def attn(self, n, o, cout, shift, sumsq):
+        seg, op = self.seg, self.op
         op(n + ".attn_qkv", [seg(o, cout, 1, 0, 0, n + ".attn_qkv.weight", cout, 0)], 3 * cout, shift)
         return op(n + ".attn_proj", [seg(n + ".attn", cout, 1, 0, 0, n + ".attn_proj.weight", cout, 0, mul=(KMIX_NEW64, KMIX_NEW32))], cout, shift,
                   epi="res", res=dict(src=o, resample=0, norm=False, C=cout), clip=256.0, sumsq=sumsq)
 
-    enc, cur, shift, skips = plan["enc"], "@input", 0, []
-    for bi, b in enumerate(enc):
-        n = b["name"]
-        next_norms = bi + 1 < len(enc) and enc[bi + 1]["cin"] == enc[bi + 1]["cout"]
+    def enc_block(self, b, cur, shift, next_norms):
+        """-> (output label, shift): the first 3x3 conv, or an encoder block (pixel-normed input, optional 1x1 skip conv in front, normed residual)"""
+        seg, op, n = self.seg, self.op, b["name"]
         if b["kind"] == "conv":
-            o = op(n, [seg(cur, b["cin"], 9, 0, 0, n + ".weight", b["cin"], 0)], b["cout"], shift, sumsq=next_norms)
-        else:
-            b["cvec_off"] = coff; coff += b["cout"]
-            rs = 1 if b["resample"] == "down" else 0
-            shift += rs
-            xs = cur
-            if b["cin"] != b["cout"]:
-                xs = op(n + ".conv_skip", [seg(cur, b["cin"], 1, rs, 0, n + ".conv_skip.weight", b["cin"], 0)], b["cout"], shift, sumsq=True)
-                rs = 0
-            y1 = op(n + ".conv_res0", [seg(xs, b["cout"], 9, rs, 2, n + ".conv_res0.weight", b["cout"], 0)], b["cout"], shift, epi="emb", cvec_off=b["cvec_off"])
-            o = op(n + ".conv_res1", [seg(y1, b["cout"], 9, 0, 0, n + ".conv_res1.weight", b["cout"], 0, mul=(KMIX_NEW64, KMIX_NEW32))], b["cout"], shift, epi="res",
-                   res=dict(src=xs, resample=rs, norm=True, C=b["cout"]), clip=0.0 if b["attn"] else 256.0, sumsq=next_norms and not b["attn"])
-            if b["attn"]:
-                o = attn(n, o, b["cout"], shift, next_norms)
-        cur = o
-        skips.append((o, b["cout"]))
-    for b in plan["dec"]:
-        n = b["name"]
-        b["cvec_off"] = coff; coff += b["cout"]
-        skip, skip_c = skips.pop() if b.get("concat") else (None, 0)
+            return op(n, [seg(cur, b["cin"], 9, 0, 0, n + ".weight", b["cin"], 0)], b["cout"], shift, sumsq=next_norms), shift
+        coff = self.cvec_off(b)
+        rs = 1 if b["resample"] == "down" else 0
+        shift += rs
+        xs = cur
+        if b["cin"] != b["cout"]:
+            xs = op(n + ".conv_skip", [seg(cur, b["cin"], 1, rs, 0, n + ".conv_skip.weight", b["cin"], 0)], b["cout"], shift, sumsq=True)
+            rs = 0
+        y1 = op(n + ".conv_res0", [seg(xs, b["cout"], 9, rs, 2, n + ".conv_res0.weight", b["cout"], 0)], b["cout"], shift, epi="emb", cvec_off=coff)
+        o = op(n + ".conv_res1", [seg(y1, b["cout"], 9, 0, 0, n + ".conv_res1.weight", b["cout"], 0, mul=(KMIX_NEW64, KMIX_NEW32))], b["cout"], shift, epi="res",
+               res=dict(src=xs, resample=rs, norm=True, C=b["cout"]), clip=0.0 if b["attn"] else 256.0, sumsq=next_norms and not b["attn"])
+        if b["attn"]:
+            o = self.attn(n, o, b["cout"], shift, next_norms)
+        return o, shift
+
+    def dec_block(self, b, cur, shift, skip=None, skip_c=0, t=0.5):
+        """-> (output label, shift): a decoder block; with `skip` its input is mp_concat([cur, skip]) (the U-Net), without (the autoencoder) `cur` alone, and a
+        channel change then rides on conv_res1 as ONE untransformed 1x1 tail with mul = kMixRes * 1"""
+        seg, op, n = self.seg, self.op, b["name"]
+        coff = self.cvec_off(b)
         rs = 2 if b["resample"] == "up" else 0
         shift -= 1 if rs else 0
         cx = b["cin"] - skip_c
         sa64 = sb64 = sa32 = sb32 = 1.0
-        if b.get("concat"):
+        if skip is not None:
             sa64, sb64 = mp_concat_scales(cx, skip_c, t)
             sa32, sb32 = F32(sa64), F32(sb64)
         w0 = n + ".conv_res0.weight"
         s0 = [seg(cur, cx, 9, rs, 1, w0, b["cin"], 0, scale=(sa64, sa32))]
-        if b.get("concat"):
+        if skip is not None:
             s0.append(seg(skip, skip_c, 9, 0, 1, w0, b["cin"], cx, scale=(sb64, sb32)))
-        y1 = op(n + ".conv_res0", s0, b["cout"], shift, epi="emb", cvec_off=b["cvec_off"])
+        y1 = op(n + ".conv_res0", s0, b["cout"], shift, epi="emb", cvec_off=coff)
         s1 = [seg(y1, b["cout"], 9, 0, 0, n + ".conv_res1.weight", b["cout"], 0, mul=(KMIX_NEW64, KMIX_NEW32))]
         res = None
         if b["cin"] != b["cout"]:
             ws = n + ".conv_skip.weight"
             s1.append(seg(cur, cx, 1, rs, 0, ws, b["cin"], 0, mul=(KMIX_RES64 * sa64, _mul32(KMIX_RES32, sa32))))
-            if b.get("concat"):
+            if skip is not None:
                 s1.append(seg(skip, skip_c, 1, 0, 0, ws, b["cin"], cx, mul=(KMIX_RES64 * sb64, _mul32(KMIX_RES32, sb32))))
         else:
             res = dict(src=cur, resample=rs, norm=False, C=b["cout"])
         o = op(n + ".conv_res1", s1, b["cout"], shift, epi="res", res=res, clip=0.0 if b["attn"] else 256.0)
         if b["attn"]:
-            o = attn(n, o, b["cout"], shift, False)
-        cur = o
-    op("out_conv", [seg(cur, plan["final_c"], 9, 0, 0, "out_conv.weight", plan["final_c"], 0)], cfg.get("out_channels") or cfg["in_channels"], shift, out_f32=True)
-    return ops, coff
+            o = self.attn(n, o, b["cout"], shift, False)
+        return o, shift
+
+
+def describe(cfg):
+    """Every fused conv op the engine emits for `cfg`, in execution order (mirror of csrc/model_graph.h, kind 0; tests/test_ae_conv_ops_cpu.py holds it to that
+    graph field for field).  Sizes are relative: `shift` = log2 of the downsampling of the op's map against the network input."""
+    plan = build_plan(cfg)
+    t = cfg.get("concat_balance", 0.3)
+    g = _Graph(modulated=True)
+    enc, cur, shift, skips = plan["enc"], "@input", 0, []
+    for bi, b in enumerate(enc):
+        cur, shift = g.enc_block(b, cur, shift, bi + 1 < len(enc) and enc[bi + 1]["cin"] == enc[bi + 1]["cout"])
+        skips.append((cur, b["cout"]))
+    for b in plan["dec"]:
+        skip, skip_c = skips.pop() if b.get("concat") else (None, 0)
+        cur, shift = g.dec_block(b, cur, shift, skip, skip_c, t)
+    g.op("out_conv", [g.seg(cur, plan["final_c"], 9, 0, 0, "out_conv.weight", plan["final_c"], 0, gain="out_gain")], cfg.get("out_channels") or cfg["in_channels"], shift,
+         out_f32=True)
+    return g.ops, g.coff
+
+
+def describe_ae(cfg, kind):
+    """The same for one stack of the EDMAutoencoder (kind 1: the encoder alone, out_conv on the bottleneck; kind 2: the skip-less decoder behind the 1x1
+    decoder_conv), from tests/_ae_twin.py's `ae_plan`.  -> (ops, width of the row of ones every modulated epilogue reads: the stack's largest cout, at least 64).
+    What no U-Net plan has: `decoder_conv` (one tap, latent + direct + ones channels straight from the staged input); a channel-changing decoder block's
+    conv_res1 with a SINGLE tail (mul = kMixRes, no concat scale); `encoder.out_conv` (2 * latent_channels fp32 couts at the deepest level); `shift` < 0 (the
+    decoder's maps grow from the latent); cvec_off = 0 everywhere."""
+    import _ae_twin
+    plan = _ae_twin.ae_plan(cfg)
+    L, D = cfg["latent_channels"], len(cfg.get("direct_skips") or [])
+    g = _Graph(modulated=False)
+    cur, shift = "@input", 0
+    if kind == 1:
+        enc = plan["enc"]
+        for bi, b in enumerate(enc):
+            cur, shift = g.enc_block(b, cur, shift, bi + 1 < len(enc) and enc[bi + 1]["cin"] == enc[bi + 1]["cout"])
+        g.op("encoder.out_conv", [g.seg(cur, plan["enc_c"], 9, 0, 0, "encoder.out_conv.weight", plan["enc_c"], 0, gain="encoder.out_gain")], 2 * L, shift, out_f32=True)
+        blocks = [b for b in enc if b["kind"] == "block"]
+    else:
+        assert kind == 2
+        cur = g.op("decoder_conv", [g.seg(cur, L + D + 1, 1, 0, 0, "decoder_conv.weight", L + D + 1, 0)], plan["dec_c0"], shift)
+        for b in plan["dec"]:
+            cur, shift = g.dec_block(b, cur, shift)
+        g.op("out_conv", [g.seg(cur, plan["final_c"], 9, 0, 0, "out_conv.weight", plan["final_c"], 0, gain="out_gain")], cfg.get("out_channels") or cfg["in_channels"], shift,
+             out_f32=True)
+        blocks = plan["dec"]
+    return g.ops, max([64] + [b["cout"] for b in blocks])
+
+
+def gains_of(ops):
+    """{weight name: name of the scalar gain folded into it} of an op list"""
+    return {s["wname"]: s["gain"] for o in ops for s in o["segs"] if s["gain"]}
+
+
+def level_dim(v, shift):
+    """a map side `shift` halvings (negative: doublings) from the stack's input, with build_plan's arithmetic"""
+    for _ in range(max(shift, 0)):
+        v = (v + 1) // 2
+    return v << max(-shift, 0)
 
 
 def _resample(x, rs):
@@ -230,6 +309,13 @@ def _conv(a, w):
 
 
 KSTEP = {"bf16": 16, "fp16": 16, "fp32": 4}      # products per accumulate step of the MFMA the kernels use (32x32x16 / 16x16x32 16-bit, 16x16x4 fp32)
+
+
+def acc_steps(o, T):
+    """accumulate steps of one output element: per tap, the real channels of a K-segment in groups of KSTEP.  K / KSTEP where the channel counts are multiples of
+    the group (every block conv); more where a few real channels sit in a padded chunk -- the 3x3 input conv of 2 + 1 channels adds 9 partial sums, not 27 / 16 --
+    and the all-zero groups of the padding add nothing and round nothing"""
+    return sum(s["taps"] * ((s["C"] + KSTEP[T] - 1) // KSTEP[T]) for s in o["segs"])
 
 
 def _conv_steps32(a, w, step):
@@ -300,19 +386,24 @@ class Twin:
     """mode 'exact': float64 everywhere, exact mul factors, no rounding (the chain test against OracleUnet);
     mode 'bf16' / 'fp16' / 'fp32': the engine's operands and weights in that storage type, evaluated in float64."""
 
-    def __init__(self, cfg, sd, mode, device="cpu"):
+    def __init__(self, cfg, sd, mode, device="cpu", ops=None, gains=None, c_total=None):
+        """ops / gains / c_total: an op list in `describe`'s form, its {weight name: gain name} map and the width of a modulation row (default: the U-Net's,
+        `describe(cfg)`; for a stack of the autoencoder `describe_ae(cfg, kind)`, `gains_of(ops)` and the width of its row of ones)"""
         self.cfg, self.mode, self.dev = cfg, mode, torch.device(device)
-        self.ops, self.c_total = describe(cfg)
+        if ops is None:
+            ops, c_total = describe(cfg)
+        self.ops, self.c_total = ops, c_total
+        self.gains = gains_of(ops) if gains is None else dict(gains)
         self.by_label = {o["label"]: o for o in self.ops}
         self.folded = {}
         for o in self.ops:
             for s in o["segs"]:
                 if s["wname"] not in self.folded:
-                    out = s["wname"] == "out_conv.weight"
-                    gain = float(sd["out_gain"]) if out else 1.0
-                    # 'exact' follows OracleUnet (the chain test's reference) to the last bit, the storage-type modes follow the host that feeds the engine
-                    self.folded[s["wname"]] = fold_weight(sd[s["wname"]], gain) if mode == "exact" else \
-                        fold_host(torch.as_tensor(sd[s["wname"]]), torch.as_tensor(sd["out_gain"]).to(torch.float32) if out else 1)
+                    gn = self.gains.get(s["wname"])
+                    # 'exact' follows the float64 reference networks (OracleUnet, AETwin: the chain tests' references) to the last bit, the storage-type modes follow
+                    # the host that feeds the engine (the gain an fp32 tensor, as `load_state_dict` passes it)
+                    self.folded[s["wname"]] = fold_weight(torch.as_tensor(sd[s["wname"]]), float(sd[gn]) if gn else 1.0) if mode == "exact" else \
+                        fold_host(torch.as_tensor(sd[s["wname"]]), torch.as_tensor(sd[gn]).to(torch.float32) if gn else 1)
         self._wcache = {}
 
     def weight(self, o, i, dtype=torch.float64):
@@ -420,7 +511,7 @@ class Twin:
         out = dict(ref=ref, K=o["K"])
         if T != "exact":
             s = gain * torch.sqrt(s2)
-            ea = (C_ACC32 if T == "fp32" else C_ACC) * U * math.sqrt(o["K"] / KSTEP[T]) * torch.sqrt(s2 + v * v)
+            ea = (C_ACC32 if T == "fp32" else C_ACC) * U * math.sqrt(acc_steps(o, T)) * torch.sqrt(s2 + v * v)
             ep = zero if ep is None else ep
             if o["epi"] == "emb":
                 tot = fprop(ea + ep)
@@ -468,8 +559,8 @@ class Twin:
             q = _conv(a.double() ** 2, w * w)
             s2 = q if s2 is None else s2 + q
         key = "acc32" if T == "fp32" else "acc"
-        ratios[key] = max(ratios.get(key, 0.0), float(((v.double() - v64).abs() / (U * math.sqrt(o["K"] / KSTEP[T]) * torch.sqrt(s2 + v64 * v64)).clamp_min(1e-300)).max()))
-        ratios[key + "_s_alone"] = max(ratios.get(key + "_s_alone", 0.0), float(((v.double() - v64).abs() / (U * math.sqrt(o["K"] / KSTEP[T]) * torch.sqrt(s2)).clamp_min(1e-300)).max()))
+        ratios[key] = max(ratios.get(key, 0.0), float(((v.double() - v64).abs() / (U * math.sqrt(acc_steps(o, T)) * torch.sqrt(s2 + v64 * v64)).clamp_min(1e-300)).max()))
+        ratios[key + "_s_alone"] = max(ratios.get(key + "_s_alone", 0.0), float(((v.double() - v64).abs() / (U * math.sqrt(acc_steps(o, T)) * torch.sqrt(s2)).clamp_min(1e-300)).max()))
         if "v" in hook:
             v = hook["v"](v, A, Wt)
         if o["epi"] == "emb":
@@ -502,17 +593,17 @@ class Twin:
         return hook["out"](out) if "out" in hook else out
 
 
-def run_chain(tw, x, cvec, emulate=False, ratios=None, on_op=None):
+def run_chain(tw, x, cvec, emulate=False, ratios=None, on_op=None, hooks=None):
     """every op of the network in order, each fed the chain's own earlier outputs.  mode 'exact': the float64 network (-> stored[label] = ref).
-    emulate: the float32 emulation with the kernels' roundings (stored = what the kernel would have stored)."""
+    emulate: the float32 emulation with the kernels' roundings (stored = what the kernel would have stored); hooks: {op label: `Twin.emulate`'s hook} (tests only)."""
     T = tw.mode
     ones = torch.ones_like(x[:, :1])
-    xin = torch.cat([x, ones], 1).double()
+    xin = torch.cat([x, ones], 1).double()      # (the autoencoder's stacks stage their input the same way: image / latent channels, then the ones channel)
     stored = {"@input": xin if T == "exact" else rne(xin, T)}
     src = lambda lab: stored.get(lab) if lab.startswith("sumsq:") else stored[lab]
     for o in tw.ops:
         if emulate:
-            out = stored[o["label"]] = tw.emulate(o, src, cvec, ratios)
+            out = stored[o["label"]] = tw.emulate(o, src, cvec, ratios, hook=(hooks or {}).get(o["label"]))
             if o["sumsq"]:   # one plane, fp32
                 stored["sumsq:" + o["label"]] = (out.to(torch.float32) ** 2).sum(1)[None]
         else:
@@ -608,10 +699,17 @@ def pick_samples(n):
     return sorted(set(i for i in (0, 1, 2, 3, n // 2 + 1, n - 2, n - 1) if 0 <= i < n))[:7] if n > 6 else list(range(n))
 
 
-def check_forward(model, tw, x, t, cond, T, flavours, device="cuda", samples=None, attn_mfma=True, attn_stats=None):
+def ones_cvec(n, width, dtype=torch.float32):
+    """the modulation rows of an autoencoder stack: `td_unet::d_ones`, one shared row of ones"""
+    return torch.ones((n, width), dtype=dtype)
+
+
+def check_forward(model, tw, x, t, cond, T, flavours, device="cuda", samples=None, attn_mfma=True, attn_stats=None, cvec=None, stored_input=False):
     """All conv ops of one engine forward (already run on `model` with x) against the twin.  flavours: {label: (tag, ksplit)} from the profile labels.
     Every attention op on the way is held to tests/_attn_twin.py's criterion on its own stored input (attn_mfma: whether the plan runs bf16 attention on the MFMA
-    kernel; its statistics are appended to attn_stats).  Returns (list of per-op statistics, number of sum-of-squares planes checked)."""
+    kernel; its statistics are appended to attn_stats).  Returns (list of per-op statistics, number of sum-of-squares planes checked).
+    A stack of the autoencoder (`model`: anything with EDMUnet2D's `read_activation(n, H, W, label, max_elems=)`, `ae_stack` below): cvec = the (n, width) rows of ones
+    it reads in place of @cvec, and stored_input = True: the `@input` source is the staged `@xin` the engine stored (x then only gives n, H, W)."""
     n, _, H, W = x.shape
     samples = samples or pick_samples(n)
     dev = torch.device(device)
@@ -628,7 +726,9 @@ def check_forward(model, tw, x, t, cond, T, flavours, device="cuda", samples=Non
                 cache[label] = model.read_activation(n, H, W, label, max_elems=size(lab, planes=True))[:, sel].to(dev)
             return (cache[label], "f5") if flavours.get(lab, ("?", 1))[0].startswith("f5") else cache[label]
         if label not in cache:
-            if label == "@input":
+            if label == "@input" and stored_input:
+                cache[label] = model.read_activation(n, H, W, "@xin", max_elems=n * H * W * 64)[sel].double().to(dev)
+            elif label == "@input":
                 xi = x[sel].double().cpu()
                 cache[label] = rne(torch.cat([xi, torch.ones_like(xi[:, :1])], 1), T).to(dev)
             else:
@@ -640,10 +740,10 @@ def check_forward(model, tw, x, t, cond, T, flavours, device="cuda", samples=Non
 
     def size(label, planes=False):
         o_ = tw.by_label[label + "_proj" if label.endswith(".attn") else label]      # (the attention output has the geometry of the conv that reads it)
-        px = n * (H >> o_["shift"]) * (W >> o_["shift"])
+        px = n * level_dim(H, o_["shift"]) * level_dim(W, o_["shift"])
         return px * ((o_["cout"] + 63) // 64 * 4 + 2) if planes else px * o_["cout"]
 
-    cvec = model.read_activation(n, H, W, "@cvec").reshape(n, -1)[sel].to(dev)
+    cvec = (model.read_activation(n, H, W, "@cvec").reshape(n, -1) if cvec is None else cvec)[sel].to(dev)
     stats, nss = [], 0
     last_use = {}
     for o in tw.ops:
@@ -672,6 +772,16 @@ def check_forward(model, tw, x, t, cond, T, flavours, device="cuda", samples=Non
         if o["label"] not in last_use:
             cache.pop(o["label"], None); cache.pop("sumsq:" + o["label"], None)
     return stats, nss
+
+
+class ae_stack:
+    """one stack of an EDMAutoencoder (1 the encoder, 2 the decoder) with the read-back interface `check_forward` uses"""
+
+    def __init__(self, ae, stack):
+        self.ae, self.stack = ae, stack
+
+    def read_activation(self, n, H, W, label, max_elems=1 << 26):
+        return self.ae.read_activation(self.stack, n, H, W, label, max_elems=max_elems)
 
 
 def summary_line(name, stats, nss, wall):

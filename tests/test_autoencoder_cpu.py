@@ -103,7 +103,7 @@ def test_header_declares_the_autoencoder_entry_points():
     text = strip(open(os.path.join(ROOT, "include", "td_ae.h")).read())
     declared = set(re.findall(r"\b(td_ae_[a-z0-9_]+)\s*\(", text))
     assert declared == {"td_ae_create", "td_ae_destroy", "td_ae_num_params", "td_ae_param_info", "td_ae_set_param", "td_ae_set_prefolded", "td_ae_finalize",
-                        "td_ae_preencode", "td_ae_postencode", "td_ae_decode"}
+                        "td_ae_preencode", "td_ae_postencode", "td_ae_decode", "td_ae_read_activation"}
     assert "typedef struct td_ae_config" in text
     with tempfile.TemporaryDirectory() as d:
         for hdr in ("td_engine.h", "td_ae.h"):

@@ -1,7 +1,12 @@
 """CPU tests of the conv-op twin (tests/_conv_twin.py): (1) chained in float64 without any rounding it IS the reference network, so its segment
 order, mul factors, concat scales and resampling are the reference's; (2) a float32 emulation of the same ops with the kernels' roundings passes
 `check_op` with zero violations and yields the ratios the slack constants were fixed from; (3) `check_op` flags six kinds of kernel bug that the
-whole-tensor 2e-2 rel-RMS bound lets through."""
+whole-tensor 2e-2 rel-RMS bound lets through.
+
+The accumulation slack counts S = `_conv_twin.acc_steps` roundings, one per tap per group of 16 (4) REAL channels.  It was K / 16 (K / 4) when the constants were fixed;
+the two differ for the input conv alone (5 + 1 channels: 9 against 54 / 16), whose E_acc is therefore 1.63 x (fp32: 1.15 x) what the GPU arms first held it to -- a
+loosening of that op's criterion that rests on the count and on this emulation only.  Ratios of (2) over S (torch 2.10 CPU): acc 1.99 (tiny bf16) / 1.84 (tiny fp16) /
+2.07 (base bf16), acc32 1.74, against the recorded 2.26 / 1.74 over K / 16."""
 import math
 import os
 import sys
