@@ -29,3 +29,5 @@ from .dataset import (fill_voids, block_median, laplacian_encode, land_share, mo
                       RunningStats, calculate_stats_welford)
 from .coarse_dataset import (area_resize_width, tile_stats, crop_scores, fill_oceans_device, fill_oceans, latitude_bands,  # noqa: F401
                              build_coarse_bands)
+from .beauty import (decode_terrain, radial_spectrum, beauty_features, analyze_terrain_frequency, calculate_beauty_score, beauty_class,  # noqa: F401
+                     assign_beauty_scores)

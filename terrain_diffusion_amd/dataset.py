@@ -273,12 +273,16 @@ def _check_prepare(highres_dem, scaled_base_lowres_dem, lowres_size, lowres_sigm
 
 
 @torch.no_grad()
-def prepare_chunks(highres_dem, scaled_base_lowres_dem, lowres_size, lowres_sigma, num_chunks=1, edge_margin=0, chunk_id=None, *, engine=None):
+def prepare_chunks(highres_dem, scaled_base_lowres_dem, lowres_size, lowres_sigma, num_chunks=1, edge_margin=0, chunk_id=None, *, beauty_scores=False,
+                   engine=None):
     """elevation_dataset.py:218-219 and 228-301 for arrays already at highres_size: highres_dem (voids as NaN, see mask_voids) and
     scaled_base_lowres_dem, both (highres_size, highres_size).  The margin crop, the void fill (radius 32), the signed square root, lowres_exact
     (the block median over highres_size // lowres_size), laplacian_encode(..., lowres_size - 2 * edge_margin, lowres_sigma) and the land share.
     Returns the reference's list of dicts, one per sub-chunk in row-major order: residual, lowfreq, lowres_exact (fp32 device tensors, views of
-    the whole planes), pct_land (float), chunk_id, subchunk_id; `climate` is absent.  One device-to-host copy per call: the land counts."""
+    the whole planes), pct_land (float), chunk_id, subchunk_id; `climate` is absent.  One device-to-host copy per call: the land counts.
+    beauty_scores=True adds `beauty_score` to every dict: beauty.calculate_beauty_score of its lowfreq and residual (data/preprocessing/
+    beauty_score.py), all sub-chunks in one device batch before the planes leave the device, with one more small read-back; the sub-chunk side
+    must then be a power of two in 8 .. 4096 (NotImplementedError otherwise)."""
     size, margin, ratio, boxes = _check_prepare(highres_dem, scaled_base_lowres_dem, lowres_size, lowres_sigma, num_chunks, edge_margin)
     engine, dev = _engine_for(highres_dem, engine)
     dem, base = _f32(highres_dem, dev), _f32(scaled_base_lowres_dem, dev)
@@ -292,6 +296,11 @@ def prepare_chunks(highres_dem, scaled_base_lowres_dem, lowres_size, lowres_sigm
     for k, (subchunk_id, (h0, h1, w0, w1), (l0, l1, m0, m1)) in enumerate(boxes):
         chunks.append({"residual": res[h0:h1, w0:w1], "lowfreq": lowfreq[l0:l1, m0:m1], "lowres_exact": lowres_exact[l0:l1, m0:m1],
                        "pct_land": float(counts[k]) / float((l1 - l0) * (m1 - m0)), "chunk_id": chunk_id, "subchunk_id": subchunk_id})
+    if beauty_scores:
+        from . import beauty
+        scores = beauty._scores(torch.stack([c["lowfreq"] for c in chunks]), torch.stack([c["residual"] for c in chunks]), engine)
+        for chunk, score in zip(chunks, scores):
+            chunk["beauty_score"] = score
     return chunks
 
 
