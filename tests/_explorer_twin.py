@@ -78,6 +78,18 @@ def quantize(rgba):
         return np.where(np.isnan(c), 0, c).astype(np.uint8)
 
 
+def passes(plane, lo, hi):
+    """The route's filter of one plane: plane >= lo and plane <= hi with the Python-float bounds brought to the plane's fp32 (a NaN fails)."""
+    plane = np.asarray(plane, F)
+    mask = np.ones(plane.shape, bool)
+    with np.errstate(invalid="ignore"):
+        if lo is not None:
+            mask &= plane >= F(lo)
+        if hi is not None:
+            mask &= plane <= F(hi)
+    return mask
+
+
 def colorize(field, lut, log1p=False, vmin=None, vmax=None, filters=()):
     """-> (rgba8 (H, W, 4), vmin, vmax, margin).  filters: (plane, lo or None, hi or None)."""
     d = display(field, log1p)
@@ -86,12 +98,8 @@ def colorize(field, lut, log1p=False, vmin=None, vmax=None, filters=()):
     rgba, margin = lookup(normalize(d, vmin, vmax), lut)
     if filters:
         mask = np.ones(d.shape, bool)
-        with np.errstate(invalid="ignore"):
-            for plane, lo, hi in filters:
-                if lo is not None:
-                    mask &= np.asarray(plane, F) >= F(lo)
-                if hi is not None:
-                    mask &= np.asarray(plane, F) <= F(hi)
+        for plane, lo, hi in filters:
+            mask &= passes(plane, lo, hi)
         rgba[~mask, :3] *= F(0.3)
     return quantize(rgba), vmin, vmax, margin
 
@@ -162,6 +170,37 @@ def land_tiles(elev_m, half, min_land_frac, exact=False):
     else:
         valid = (c.astype(F) / F(cells)).astype(np.float64) >= min_land_frac
     return (i * W + j)[valid].astype(np.int64)
+
+
+def block_offsets(counts, round_size=1024):
+    """Exclusive prefix sums of the per-block counts and their total, taken as the device takes them: in rounds of `round_size` blocks with
+    the sum of all earlier rounds carried into the next."""
+    counts = np.asarray(counts, np.int64)
+    out, carry = np.zeros(counts.size, np.int64), 0
+    for base in range(0, counts.size, round_size):
+        part = counts[base:base + round_size]
+        out[base:base + round_size] = carry + np.cumsum(part) - part
+        carry += int(part.sum())
+    return out, carry
+
+
+def compact(valid, offsets=block_offsets, block=256):
+    """The ordered compaction of an (H, W) validity mask as the device states it: blocks of `block` consecutive flat indices, their counts,
+    `offsets(counts)`, and each block's valid indices written from its offset on -> (idx, count).  Equal to np.flatnonzero(valid) when
+    `offsets` is right; slots nobody wrote hold -1."""
+    flat = np.asarray(valid, bool).ravel()
+    nb = -(-flat.size // block)
+    padded = np.zeros(nb * block, bool)
+    padded[:flat.size] = flat
+    counts = padded.reshape(nb, block).sum(1)
+    off, total = offsets(counts)
+    idx = np.full(int(counts.sum()), -1, np.int64)
+    where = np.flatnonzero(padded)
+    rank = np.arange(where.size) - np.repeat(np.cumsum(counts) - counts, counts)        # position within its block
+    at = np.repeat(off, counts) + rank
+    ok = at < idx.size
+    idx[at[ok]] = where[ok]
+    return idx, int(total)
 
 
 def sample_land_tiles(coarse, coarse_window, detail_size, min_land_frac=0.5, n_samples=10):
