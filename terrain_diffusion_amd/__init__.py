@@ -31,3 +31,5 @@ from .coarse_dataset import (area_resize_width, tile_stats, crop_scores, fill_oc
                              build_coarse_bands)
 from .beauty import (decode_terrain, radial_spectrum, beauty_features, analyze_terrain_frequency, calculate_beauty_score, beauty_class,  # noqa: F401
                      assign_beauty_scores)
+from .train_data import (DeviceGroups, views, sample_latents, cond_image, cond_vector, H5LatentsDataset, H5DecoderTerrainDataset,  # noqa: F401
+                         H5AutoencoderDataset)
