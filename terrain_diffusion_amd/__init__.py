@@ -33,3 +33,4 @@ from .beauty import (decode_terrain, radial_spectrum, beauty_features, analyze_t
                      assign_beauty_scores)
 from .train_data import (DeviceGroups, views, sample_latents, cond_image, cond_vector, H5LatentsDataset, H5DecoderTerrainDataset,  # noqa: F401
                          H5AutoencoderDataset)
+from .objective import (noise_levels, add_noise, logvar, squared_error, v_loss, terrain_uint8, validation_loss, noise_loss_curve)  # noqa: F401

@@ -39,6 +39,8 @@ class EDMUnet2D:
                            emb_channels=emb_channels, noise_emb_dims=noise_emb_dims, attn_resolutions=list(attn_resolutions or []),
                            midblock_attention=midblock_attention, concat_balance=concat_balance, conditional_inputs=conds,
                            fourier_scale=fourier_scale)
+        self.n_logvar = int(n_logvar)
+        self._logvar_ops = None
         self.dtype = dtype
         self.engine = get_engine(device)
         self.device = torch.device("cuda", self.engine.device_id)
@@ -115,6 +117,7 @@ class EDMUnet2D:
         self._finalized = True
         # the caller's (raw, un-folded) tensors are kept by reference for state_dict() / save_pretrained(): the engine only holds packed weights
         self._state = {k: state_dict[k] for k in state_dict if k in exp or k.startswith("logvar_")}
+        self._logvar_ops = None
         return self
 
     def state_dict(self):
@@ -152,9 +155,11 @@ class EDMUnet2D:
         return self
 
     # ---- model(x, noise_labels, conditional_inputs)  (edm_unet.py:161-184)
-    def __call__(self, x, noise_labels, conditional_inputs=None):
+    def __call__(self, x, noise_labels, conditional_inputs=None, return_logvar=False):
         if not self._finalized:
             raise RuntimeError("load_state_dict first")
+        if return_logvar:
+            self.logvar_operands()              # a checkpoint without the head fails here, before anything is launched
         x = f32(x)
         n, _, H, W = x.shape
         t = f32(noise_labels, "cpu").flatten()
@@ -167,9 +172,37 @@ class EDMUnet2D:
         cond = self.cond_rows(conditional_inputs, n, x.device)
         out = torch.empty((n, self.config["out_channels"], H, W), dtype=torch.float32, device=x.device)
         check(lib().td_unet_forward(self._h, n, H, W, ptr(x), ptr(t), ptr(cond), ptr(out)))
+        if return_logvar:
+            return out, self.logvar(t.to(x.device)).reshape(-1, 1, 1, 1)
         return out
 
     forward = __call__
+
+    def logvar_operands(self):
+        """(freqs, phases, folded weight) of the logvar head as device tensors (K each), from the kept logvar_* tensors; KeyError when the
+        checkpoint lacks them.  The weight is folded by the fold the convolutions use (the reference's fp32 bits)."""
+        if not self._finalized:
+            raise RuntimeError("load_state_dict first")
+        if self.n_logvar != 1:
+            raise NotImplementedError(f"n_logvar={self.n_logvar}: the reference's reshape(-1, 1, 1, 1) only broadcasts for 1")
+        if self._logvar_ops is None:
+            names = ("logvar_fourier.freqs", "logvar_fourier.phases", "logvar_linear.weight")
+            lacking = [k for k in names if k not in self._state]
+            if lacking:
+                raise KeyError(f"the checkpoint lacks {lacking}: return_logvar needs the logvar head")
+            f, p, w = (torch.as_tensor(self._state[k]).detach().to("cpu", torch.float32) for k in names)
+            if w.dim() != 2 or w.shape[0] != 1 or w.shape[1] != f.numel() or p.numel() != f.numel():
+                raise ValueError(f"logvar head: weight {tuple(w.shape)}, freqs {tuple(f.shape)}, phases {tuple(p.shape)}")
+            self._logvar_ops = tuple(a.reshape(-1).contiguous().to(self.device) for a in (f, p, self._fold_reference(w, 1)))
+        return self._logvar_ops
+
+    def logvar(self, noise_labels):
+        """The head of edm_unet.py:181-183 for device noise_labels (n): logvar_linear(logvar_fourier(log(tan(t) / 8))), (n) fp32 on the device,
+        by libtd_objective.so from the kept logvar_* tensors (fp32; the reference's bf16 autocast of this linear is not reproduced)."""
+        from . import objective
+        ops = self.logvar_operands()
+        table = objective.noise_levels(noise_labels, mode="t", sigma_data=1.0, engine=self.engine)
+        return objective.logvar(table, *ops, engine=self.engine)
 
     def cond_rows(self, conditional_inputs, n, device=None):
         """conditional_inputs (list, reference order: (n,dim) tensors for 'tensor' inputs, (n,) or (1,) for 'float' inputs)
